@@ -18,6 +18,14 @@ is fixed work split across N GPUs.
 Usage (driver contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line.  ``--dump-outputs DIR`` additionally writes what the last timed step
+returned (``DIR/<name>.npy``, float64) so two builds can be compared output
+for output: inputs and weights are seeded, identical from run to run.
+``--full`` adds the checks that are not part of the headline figure (the
+9-dim finalReward golden assertion, reported as
+``config.final_reward_100spans``).
 """
 
 from __future__ import annotations
@@ -113,7 +121,14 @@ def main() -> int:
                     help="tensor-parallel scoring over the whole world (config 5) "
                          "instead of candidate-parallel DP")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks beside the headline figure "
+                         "(finalReward golden assertion)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank, world = P.init_from_env()
     n_gpus = max(args.gpus, world)
@@ -174,7 +189,7 @@ def main() -> int:
             scores = P.dp_scores_allreduce(n_candidates, my_cands, my_scores, comm_dev)
         # Top-K beam selection (deterministic, every rank)
         order = sorted(range(n_candidates), key=lambda i: (-scores[i], i))
-        return [order[i] for i in range(args.beam_width)], scores
+        return [order[i] for i in range(args.beam_width)], scores, lps
 
     # warmup
     for i in range(args.warmup):
@@ -186,7 +201,7 @@ def main() -> int:
     t0 = time.perf_counter()
     beam = None
     for i in range(args.steps):
-        beam, scores = one_step(i)
+        beam, scores, lps = one_step(i)
     if dist.is_initialized():
         dist.barrier()
     if use_cuda:
@@ -199,6 +214,17 @@ def main() -> int:
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t[0])
+
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step handed back: the all-reduced candidate
+        # scores, the Top-K beam, and this rank's per-sequence log-probs
+        # (candidate-major; all of them at --gpus 1).  A few KB in total.
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, val in (("scores", scores), ("beam_topk", beam),
+                          ("sequence_logprobs", lps)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    np.asarray(val, dtype=np.float64))
 
     if rank == 0:
         ips = args.steps / elapsed
@@ -225,10 +251,11 @@ def main() -> int:
                 "branch_factor": args.branch_factor,
                 "gradient_batch_size": args.rollouts,
                 "candidates_per_iteration": n_candidates,
-                "final_reward_100spans": final_reward_check(),
                 "beam_topk": beam,
             },
         }
+        if args.full:
+            result["config"]["final_reward_100spans"] = final_reward_check()
         print(json.dumps(result))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -1,15 +1,16 @@
 #!/bin/bash
 # Re-emit the per-config benchmark records with round-2 kernels and the
 # fixed per-config metric labels.  Run on an MI355X box.
+# --full: the records carry the finalReward golden check beside the figure.
 set -x
 cd "$(dirname "$0")/.."
-mkdir -p benchmarks/results gpurun_out
+mkdir -p benchmarks/results/logs
 
 run() {  # name, args...
   local name=$1; shift
-  timeout 900 python bench.py "$@" 2>gpurun_out/cfg_${name}.err \
+  timeout 900 python bench.py --full "$@" 2>benchmarks/results/logs/cfg_${name}.err \
     | tail -1 > benchmarks/results/r02_bench_${name}.json
-  tail -3 gpurun_out/cfg_${name}.err
+  tail -3 benchmarks/results/logs/cfg_${name}.err
   cat benchmarks/results/r02_bench_${name}.json
 }
 

@@ -37,6 +37,17 @@ def daemon():
     proc.wait(timeout=10)
 
 
+@pytest.fixture
+def short_sock():
+    """A socket path short enough for sun_path (~107 bytes) wherever pytest
+    keeps tmp_path: a private directory under /tmp, like the daemon fixture."""
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="senweaver_", dir="/tmp")
+    yield os.path.join(d, "d.sock")
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def test_daemon_ping(daemon):
     c = DaemonClient(daemon[0])
     assert c.ping(timeout=120)  # first ping waits for engine import/ready
@@ -169,26 +180,29 @@ def test_daemon_worker_crash_errors_inflight(daemon):
     pids = [int(x) for x in out.stdout.split()]
     assert pids, "engine worker child process not found"
 
+    # freeze the worker first: on a fast machine the tiny model can finish
+    # the whole request before the kill below, and nothing is in flight then
+    os.kill(pids[0], signal.SIGSTOP)
     done = threading.Event()
     errors = []
     rid = c.send_llm_message([{"role": "user", "content": "doomed request"}],
                              on_final=lambda m: done.set(),
                              on_error=lambda m: (errors.append(m), done.set()),
                              max_new_tokens=512)
-    time.sleep(0.3)  # let the request reach the worker
+    time.sleep(0.3)  # let the request reach the daemon
     os.kill(pids[0], signal.SIGKILL)
     assert done.wait(timeout=60), "in-flight request hung after worker crash"
     assert errors and "crash" in errors[0].get("message", "")
     c.close()
 
 
-def test_cli_singleton_start_status_stop(tmp_path, monkeypatch):
+def test_cli_singleton_start_status_stop(tmp_path, monkeypatch, short_sock):
     """Launcher CLI (server/cli.py = the Rust code-cli's engine subset):
     singleton lock, start/status/stop, stale-lock reclaim."""
     from senweaver_amd.server import cli
 
     monkeypatch.setattr(cli, "STATE_DIR", str(tmp_path))
-    monkeypatch.setattr(cli, "SOCKET_PATH", str(tmp_path / "d.sock"))
+    monkeypatch.setattr(cli, "SOCKET_PATH", short_sock)
     monkeypatch.setattr(cli, "LOCK_PATH", str(tmp_path / "d.lock"))
     monkeypatch.setattr(cli, "LOG_PATH", str(tmp_path / "d.log"))
     monkeypatch.setenv("SENWEAVER_MODEL", "tiny-debug")
@@ -271,14 +285,14 @@ def test_daemon_model_options_sampling(daemon):
     c.close()
 
 
-def test_cli_one_shot_generate(tmp_path):
+def test_cli_one_shot_generate(tmp_path, short_sock):
     """`senweaver-daemon generate` front door: auto-start, stream to
     stdout, daemon reusable after, clean stop."""
     import subprocess
     import sys
     env = dict(os.environ,
                SENWEAVER_STATE_DIR=str(tmp_path),
-               SENWEAVER_SOCKET=str(tmp_path / "d.sock"),
+               SENWEAVER_SOCKET=short_sock,
                SENWEAVER_MODEL="tiny-debug", SENWEAVER_MAX_SEQ="128")
     r = subprocess.run([sys.executable, "-m", "senweaver_amd.server.cli",
                         "generate", "--max-new", "6", "one shot"],
@@ -298,12 +312,12 @@ def test_cli_one_shot_generate(tmp_path):
     assert r2.returncode == 0
 
 
-def test_daemon_crash_loop_breaker(tmp_path):
+def test_daemon_crash_loop_breaker(short_sock):
     """A worker that can never start (bogus model) must NOT respawn
     forever: after 3 fast crashes the daemon exits, the socket is gone,
     and the launcher reports it down."""
     bin_path = build_daemon()
-    sock = str(tmp_path / "d.sock")
+    sock = short_sock
     env = dict(os.environ, SENWEAVER_MODEL="no-such-model")
     proc = subprocess.Popen([bin_path, "--socket", sock], env=env,
                             stderr=subprocess.PIPE, text=True)

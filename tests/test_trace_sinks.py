@@ -43,8 +43,11 @@ def test_file_sink_incremental_watermark(tmp_path):
     assert json.loads(lines[1])["traces"][0]["id"]  # delta payload
 
 
-def test_uds_sink_end_to_end(tmp_path):
-    sock_path = str(tmp_path / "collector.sock")
+def test_uds_sink_end_to_end(tmp_path, monkeypatch):
+    # sun_path holds ~107 bytes and pytest's tmp_path can be deeper than
+    # that: bind/connect by a name relative to the temp dir instead
+    monkeypatch.chdir(tmp_path)
+    sock_path = "collector.sock"
     received = []
     srv = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     srv.bind(sock_path)
@@ -83,11 +86,11 @@ def test_uds_sink_end_to_end(tmp_path):
     assert "rewardSummary" in received[0] or "summary" in received[0]["traces"][0]
 
 
-def test_uds_sink_failure_keeps_watermark(tmp_path):
+def test_uds_sink_failure_keeps_watermark(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)  # short relative socket name, as above
     tc = TraceCollector()
     _mk_traces(tc, 2, "w")
-    res = tc.upload_to_sink(UDSSink(str(tmp_path / "nonexistent.sock"),
-                                    timeout=0.5))
+    res = tc.upload_to_sink(UDSSink("nonexistent.sock", timeout=0.5))
     assert not res["success"]
     # nothing marked uploaded: the next (working) sink gets everything
     got = tc.upload_to_sink(FileSink(str(tmp_path / "t.jsonl")))
