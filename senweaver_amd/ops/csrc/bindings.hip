@@ -246,7 +246,8 @@ torch::Tensor gemm_bt(torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(B.size(1) == K, "K mismatch");
   auto C = torch::empty({M, N}, A.options());
   if (M <= 16) {
-    TORCH_CHECK(N % 4 == 0 && K % 512 == 0, "gemv path needs N%4==0, K%512==0");
+    TORCH_CHECK(N % 4 == 0 && K >= 512 && K % 512 == 0,
+                "gemv path needs N%4==0, K%512==0 (K >= 512)");
     // wave-per-row coalesced GEMV; A must be padded to the MM bucket rows
     int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
     torch::Tensor Ap = A;
@@ -422,6 +423,11 @@ std::vector<torch::Tensor> gemv_norm_bt(torch::Tensor x, c10::optional<torch::Te
   check_bf16(B, "B");
   const int M = x.size(0), K = x.size(1), N = B.size(0);
   TORCH_CHECK(M <= 16 && N % 4 == 0 && K % 512 == 0 && B.size(1) == K);
+  // the kernel reads K norm weights and an [M, K] residual unconditionally
+  TORCH_CHECK(normw.numel() == K, "gemv_norm_bt: normw must have K elements");
+  TORCH_CHECK(!res_in.has_value() ||
+                  (res_in->dim() == 2 && res_in->size(0) == M && res_in->size(1) == K),
+              "gemv_norm_bt: res_in must be [M, K]");
   auto C = torch::empty({M, N}, x.options());
   auto res_out = torch::empty({M, K}, x.options());
   int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
@@ -711,7 +717,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_bt_v3", [](torch::Tensor a, torch::Tensor b) {
     check_bf16(a, "a"); check_bf16(b, "b");
     const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(M == 1 && K % 512 == 0 && K <= 14336 && N % 8 == 0);
+    // both kernels walk K in 1024-element steps (two 512 slots per barrier
+    // round): K % 1024 != 0 would drop the last slot, and K = 512 would run
+    // no step while the loader prologue still fetches 1024 elements per row
+    TORCH_CHECK(M == 1 && K >= 1024 && K % 1024 == 0 && K <= 14336 &&
+                N >= 8 && N % 8 == 0 && b.size(1) == K,
+                "gemv_bt_v3 needs M==1, K%1024==0, 1024<=K<=14336, N%8==0");
     auto C = torch::empty({M, N}, a.options());
     if (K <= 4096)
       gemv_bt_bf16_v3_m1<<<dim3(N / 8), dim3(256), 0, cur_stream()>>>(
@@ -726,7 +737,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     check_bf16(x, "x");
     TORCH_CHECK(bq.scalar_type() == torch::kUInt8 && bs.scalar_type() == torch::kFloat32);
     const int M = x.size(0), K = x.size(1), N = bq.size(0);
-    TORCH_CHECK(M >= 1 && M <= 8 && K % 1024 == 0 && bq.size(1) == K && N % 4 == 0);
+    TORCH_CHECK(M >= 1 && M <= 8 && K >= 1024 && K % 1024 == 0 && bq.size(1) == K &&
+                N % 4 == 0 && bs.numel() == N);
+    TORCH_CHECK(bq.is_contiguous() && bs.is_contiguous());
     const int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
     torch::Tensor xp = x;
     if (M < MM) {
@@ -754,8 +767,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     check_bf16(x, "x");
     TORCH_CHECK(bq.scalar_type() == torch::kUInt8 && bs.scalar_type() == torch::kUInt8);
     const int M = x.size(0), K = x.size(1), N = bq.size(0);
-    TORCH_CHECK(M >= 1 && M <= 8 && K % 1024 == 0 && bq.size(1) == K &&
-                bs.size(1) == K / 32 && N % 4 == 0);
+    TORCH_CHECK(M >= 1 && M <= 8 && K >= 1024 && K % 1024 == 0 && bq.size(1) == K &&
+                bs.dim() == 2 && bs.size(0) == N && bs.size(1) == K / 32 && N % 4 == 0);
+    TORCH_CHECK(bq.is_contiguous() && bs.is_contiguous());
     const int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
     torch::Tensor xp = x;
     if (M < MM) {

@@ -314,14 +314,21 @@ gemm_bt_bf16_256_kernel(const ushort* __restrict__ A, const ushort* __restrict__
 // of the achievable HBM rate: its in-flight requests are single 1 KiB row
 // chunks scattered across many DRAM pages.  The microarch price list
 // (ldsdma-fill / nt-weights rows) measures 6.5-6.8 TB/s chip-wide when each
-// CU streams CONTIGUOUS 16 KiB fills via global_load_lds with nt.  Here a
-// block owns 16 consecutive output rows and walks K in 512-element chunks:
-// slot = 16 rows x 1 KiB, ring of 5 slots in LDS (<= 3 in flight keeps the
-// counted vmcnt under the 6-bit 63 cap), wave 3 is loader AND consumer, all
-// 4 waves split the 16 rows (16 lanes per row, 32 elems per lane per slot),
-// x is staged to LDS once up front.  One barrier per slot; counted
-// s_waitcnt vmcnt(16*inflight) before it (wait-then-barrier).
-// Constraints: M == 1, K % 512 == 0, N % 16 == 0.
+// CU streams CONTIGUOUS fills via global_load_lds with nt.  Here a block
+// owns 8 consecutive output rows and walks K in 512-element chunks:
+// slot = 8 rows x 1 KiB = 8 KiB in an LDS ring, wave 3 is loader AND
+// consumer, each of the 4 waves owns 2 of the 8 rows (64 lanes x 8 elems
+// per row per slot), x is staged to LDS once up front; counted
+// s_waitcnt vmcnt(8*slots in flight) before each barrier (wait-then-barrier).
+//
+// gemv3_body (one slot per barrier, ring of RD) is the first form and is no
+// longer launched; it needs M == 1, K % 512 == 0, N % 8 == 0.
+// gemv3_body2 (two slots per barrier, ring of 6) serves every launched
+// kernel — gemv_bt_bf16_v3_m1 (K <= 4096), gemv_bt_bf16_v3w_m1 and
+// swiglu_gemv_bt_bf16_m1 (K <= 14336).  Constraints: M == 1,
+// K % 1024 == 0 and K >= 1024 (a step is 1024 elements: an odd slot count
+// would lose the last slot, and the prologue fetches step 0 unconditionally),
+// K <= XCAP, N % 8 == 0 (grid N/8, every block reads 8 full rows).
 // ---------------------------------------------------------------------------
 #define GV3_KW 512         /* chunk elems per row per slot */
 

@@ -102,7 +102,11 @@ def paged_decode_attn_ref(q, kcache, vcache, block_table, ctx_lens, scale):
 
 
 def argmax_rows_ref(logits: torch.Tensor) -> torch.Tensor:
-    return logits.float().argmax(dim=-1).to(torch.int32)
+    """Lowest index of the row maximum; NaN entries are ignored (as in the
+    kernel, where NaN never wins a comparison), an all-NaN row gives 0."""
+    x = logits.float()
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+    return x.argmax(dim=-1).to(torch.int32)
 
 
 def target_logprob_ref(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:

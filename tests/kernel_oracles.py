@@ -1,0 +1,649 @@
+"""fp64 oracles, input generators and error bounds for the decode kernels.
+
+Helper module for test_kernel_oracles_cpu.py and test_decode_edges_gpu.py
+(no tests live here).  Every oracle takes the SAME bf16 / uint8 tensors the
+kernel gets, upcasts with ``.double()`` and computes in plain torch on the
+CPU, so the only error in an oracle is fp64 rounding (~1e-16 relative).
+
+Bounds are derived from the number formats, never from kernel output:
+
+* bf16 has 8 significand bits, so rounding a result r to bf16 (RNE) moves
+  it by at most half an ulp, which lies between 2^-9 |r| (r just below a
+  power of two) and 2^-8 |r| (just above); the bounds allow 2^-8 |r|.
+* fp32 accumulation of K exact products in ANY order is off by at most
+  (K-1) 2^-24 sum|x_k w_k| to first order (bf16 x bf16 and e4m3 x bf16
+  products are exact in fp32: 8+8 and 4+8 significand bits).
+"""
+
+from __future__ import annotations
+
+import math
+
+import torch
+
+BF16 = torch.bfloat16
+U_BF16_OUT = 2.0 ** -8   # bf16 unit roundoff: half an ulp <= 2^-8 |r|
+U_FP32 = 2.0 ** -24      # fp32 unit roundoff
+
+
+# --------------------------------------------------------------------------
+# bit-level comparison
+# --------------------------------------------------------------------------
+def bits(t: torch.Tensor) -> torch.Tensor:
+    """bf16 tensor -> its int16 bit pattern on the CPU (NaN / -0 aware)."""
+    assert t.dtype == BF16
+    return t.detach().cpu().contiguous().view(torch.int16)
+
+
+def assert_bits_equal(got: torch.Tensor, exp: torch.Tensor, what: str = ""):
+    assert got.shape == exp.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(exp.shape)}"
+    g, e = bits(got), bits(exp)
+    if torch.equal(g, e):
+        return
+    bad = (g != e).nonzero()
+    i = tuple(int(v) for v in bad[0])
+    raise AssertionError(
+        f"{what}: {bad.shape[0]} of {g.numel()} elements differ bitwise; first at "
+        f"{i}: got {float(got.detach().cpu()[i])!r} expected {float(exp.detach().cpu()[i])!r}")
+
+
+def assert_within(got: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, what: str = ""):
+    """|got - ref64| <= bound elementwise (bound broadcastable); NaN fails."""
+    err = (got.detach().cpu().double() - ref64).abs()
+    ok = err <= bound  # NaN compares False
+    if bool(ok.all()):
+        return
+    bad = (~ok).nonzero()
+    i = tuple(int(v) for v in bad[0])
+    b = bound.expand_as(err) if isinstance(bound, torch.Tensor) else torch.full_like(err, bound)
+    raise AssertionError(
+        f"{what}: {bad.shape[0]} of {err.numel()} elements out of bound; first at {i}: "
+        f"got {float(got.detach().cpu().double()[i])!r} ref {float(ref64[i])!r} "
+        f"err {float(err[i]):.3e} bound {float(b[i]):.3e}")
+
+
+def rel_fro(got: torch.Tensor, ref64: torch.Tensor) -> float:
+    g = got.detach().cpu().double()
+    return float((g - ref64).norm() / ref64.norm())
+
+
+# --------------------------------------------------------------------------
+# GEMV family
+# --------------------------------------------------------------------------
+def probe_columns(K: int) -> list:
+    """One-hot probe columns: lane 0 / lane 63 of the first iteration, both
+    8-wide halves of the fp8 16-byte step, loop-iteration (512) and step
+    (1024) boundaries, LDS ring wrap (slot 6 = column 3072) and the tail."""
+    cand = [0, 7, 8, 15, 16, 511, 512, 1023, 1024, 3071, 3072,
+            K - 1024, K - 513, K - 512, K - 1]
+    return sorted({c for c in cand if 0 <= c < K})
+
+
+def onehot_calls(M: int, K: int) -> list:
+    """Probe columns spread over the rows of ceil(P/M) calls: call c, row m
+    probes P[(c*M + m) % P], so every probe is seen at this M."""
+    P = probe_columns(K)
+    ncalls = -(-len(P) // M)
+    return [[P[(c * M + m) % len(P)] for m in range(M)] for c in range(ncalls)]
+
+
+def onehot_x(cols: list, K: int) -> torch.Tensor:
+    x = torch.zeros(len(cols), K, dtype=BF16)
+    for m, k in enumerate(cols):
+        x[m, k] = 1.0
+    return x
+
+
+def rand_bf16(gen: torch.Generator, *shape) -> torch.Tensor:
+    return torch.randn(*shape, generator=gen).to(BF16)
+
+
+def int_x(gen: torch.Generator, M: int, K: int) -> torch.Tensor:
+    """Integers in [-2, 2] as bf16 (exact)."""
+    return torch.randint(-2, 3, (M, K), generator=gen).to(BF16)
+
+
+def _rand_e4m3_bytes(gen, N, K) -> torch.Tensor:
+    """Random finite NON-ZERO e4m3fn bytes: magnitude code in [1, 0x7e]
+    (0x7f is NaN; +-0 is left out because a one-hot product with -0 would
+    be expected as -0 while an fp32 accumulator started at +0 gives +0)."""
+    mag = torch.randint(1, 0x7f, (N, K), generator=gen)
+    sign = torch.randint(0, 2, (N, K), generator=gen)
+    return (mag | (sign << 7)).to(torch.uint8)
+
+
+def _int_e4m3_bytes(gen, N, K) -> torch.Tensor:
+    """Integers in [-4, 4] as e4m3 bytes (integers <= 16 are exact)."""
+    w = torch.randint(-4, 5, (N, K), generator=gen).float()
+    return w.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def e4m3_to_f64(q: torch.Tensor) -> torch.Tensor:
+    return q.cpu().view(torch.float8_e4m3fn).float().double()
+
+
+def dequant_fp8_ref64(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """Row-scaled e4m3 weights -> fp64 [N, K]."""
+    return e4m3_to_f64(q) * s.cpu().double().unsqueeze(1)
+
+
+def dequant_mx_ref64(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """MX weights (e4m3 bytes + e8m0 byte per 32-block) -> fp64 [N, K]."""
+    N, K = q.shape
+    f = e4m3_to_f64(q).view(N, K // 32, 32)
+    sc = torch.exp2(s.cpu().double() - 127.0).unsqueeze(-1)
+    return (f * sc).reshape(N, K)
+
+
+def make_weights(kind: str, gen: torch.Generator, N: int, K: int, mode: str):
+    """Weights for one GEMV kernel family.
+
+    kind: 'bf16' | 'fp8' | 'mx'.  mode: 'random' (unsymmetric random data;
+    fp8 row scales are powers of two), 'random_scale' (fp8 only: arbitrary
+    positive row scales), 'int' (integers in [-4, 4], power-of-two scales).
+    Returns (wargs, w64): the tensors the kernel takes after x, and the
+    dequantized fp64 weight matrix [N, K].  Quantized forms are built
+    directly from bytes — the quantizer kernels are not involved.
+    """
+    if kind == "bf16":
+        w = (torch.randint(-4, 5, (N, K), generator=gen).to(BF16) if mode == "int"
+             else rand_bf16(gen, N, K))
+        return (w,), w.double()
+    q = _int_e4m3_bytes(gen, N, K) if mode == "int" else _rand_e4m3_bytes(gen, N, K)
+    if kind == "fp8":
+        if mode == "random_scale":
+            s = (2.0 ** -4) * (1.0 + torch.rand(N, generator=gen))
+        else:
+            s = torch.exp2(torch.randint(-3, 4, (N,), generator=gen).float())
+        s = s.float()
+        return (q, s), dequant_fp8_ref64(q, s)
+    if kind == "mx":
+        # e8m0 byte = exponent + 127; 2^-2 .. 2^2 keeps integer sums exact
+        s = torch.randint(125, 130, (N, K // 32), generator=gen).to(torch.uint8)
+        return (q, s), dequant_mx_ref64(q, s)
+    raise ValueError(kind)
+
+
+def is_pow2(t: torch.Tensor) -> torch.Tensor:
+    m, _ = torch.frexp(t.double())
+    return m == 0.5
+
+
+def gemv_ref64(x: torch.Tensor, w64: torch.Tensor) -> torch.Tensor:
+    """C[M,N] = x @ w^T in fp64; w is a bf16 tensor or an fp64 dequant."""
+    return x.cpu().double() @ w64.cpu().double().t()
+
+
+def gemv_abs_dot(x: torch.Tensor, w64: torch.Tensor) -> torch.Tensor:
+    """(|x| . |w|^T): the scale of the fp32 summation error term."""
+    return x.cpu().double().abs() @ w64.cpu().double().abs().t()
+
+
+def gemv_bound(ref64: torch.Tensor, absdot: torch.Tensor, K: int, kfactor: int = 1) -> torch.Tensor:
+    """2^-8 |ref| (bf16 output rounding: half an ulp never exceeds it) +
+    kfactor*K 2^-24 (|x|.|w|^T) (worst-case fp32 summation error, any order)."""
+    return U_BF16_OUT * ref64.abs() + kfactor * K * U_FP32 * absdot
+
+
+def exact_bf16(ref64: torch.Tensor) -> torch.Tensor:
+    """bf16_rne of an fp64 value that is exactly representable in fp32 (so
+    the double -> float -> bf16 chain rounds once).  Asserts that premise."""
+    f = ref64.float()
+    assert torch.equal(f.double(), ref64), "value is not exact in fp32"
+    return f.to(BF16)
+
+
+def gemv_norm_ref64(x, res, normw, b, eps):
+    """Fused add + RMSNorm + GEMV as the kernel defines it: t = x + res is
+    NOT rounded; C = (sum_k t normw b) * rsqrt(mean(t^2) + eps);
+    res_out = bf16(x + res) computed in fp32.  Returns (C64, res_out_bf16,
+    absdot64) with absdot = (|t| |normw| . |b|^T) * rsqrt(mean(t^2)+eps)."""
+    xd = x.cpu().double()
+    t = xd + res.cpu().double() if res is not None else xd
+    rs = torch.rsqrt((t * t).mean(dim=1, keepdim=True) + eps)
+    tw = t * normw.cpu().double()
+    c = (tw @ b.cpu().double().t()) * rs
+    absdot = (tw.abs() @ b.cpu().double().abs().t()) * rs
+    if res is not None:
+        res_out = (x.cpu().float() + res.cpu().float()).to(BF16)
+    else:
+        res_out = x.cpu().clone()
+    return c, res_out, absdot
+
+
+def swiglu_ref64(gateup: torch.Tensor) -> torch.Tensor:
+    """silu(g) * u in fp64, unrounded.  gateup [M, 2K] -> [M, K]."""
+    gu = gateup.cpu().double()
+    K = gu.shape[-1] // 2
+    g, u = gu[..., :K], gu[..., K:]
+    return g * torch.sigmoid(g) * u
+
+
+def swiglu_onehot_gateup(gen, k: int, K: int) -> torch.Tensor:
+    """gateup [1, 2K] whose activation is exactly 32 e_k: u = e_k, g random
+    with g_k = 32.  In fp32 1 + exp(-32) == 1, so silu(32) == 32 exactly."""
+    g = rand_bf16(gen, 1, K)
+    g[0, k] = 32.0
+    u = torch.zeros(1, K, dtype=BF16)
+    u[0, k] = 1.0
+    return torch.cat([g, u], dim=1)
+
+
+# --------------------------------------------------------------------------
+# Paged decode attention
+# --------------------------------------------------------------------------
+PAGE = 16
+NSPLIT = 8
+
+
+def probe_positions(ctx: int) -> list:
+    """Spike positions: page / 32-batch boundaries, both sides of the first
+    split boundary, a wave's second and third pass, and the last position."""
+    chunk = -(-ctx // NSPLIT)
+    cand = [0, 15, 16, 31, 32, chunk - 1, chunk, chunk + 127, chunk + 128, ctx - 1]
+    return sorted({p for p in cand if 0 <= p < ctx})
+
+
+def make_paged_case(gen, ctxs, H, Hk, D=128, qscale=1.0, spare_pages=5, spare_cols=3):
+    """Random paged-KV decode case.  Block tables are a random permutation
+    of the page pool (unused entries -1, max_pages larger than needed).
+    Returns dict(q, kcache, vcache, block_table, ctx_lens, scale)."""
+    B = len(ctxs)
+    need = [-(-c // PAGE) for c in ctxs]
+    P = sum(need) + spare_pages
+    perm = torch.randperm(P, generator=gen)
+    max_pages = max(need) + spare_cols
+    bt = torch.full((B, max_pages), -1, dtype=torch.int32)
+    o = 0
+    for b in range(B):
+        bt[b, :need[b]] = perm[o:o + need[b]].to(torch.int32)
+        o += need[b]
+    q = (torch.randn(B, H, D, generator=gen) * qscale).to(BF16)
+    kc = rand_bf16(gen, P, PAGE, Hk, D)
+    vc = rand_bf16(gen, P, PAGE, Hk, D)
+    return dict(q=q, kcache=kc, vcache=vc, block_table=bt,
+                ctx_lens=torch.tensor(ctxs, dtype=torch.int32),
+                scale=1.0 / math.sqrt(D))
+
+
+def slots_of(block_table_row: torch.Tensor, ctx: int) -> torch.Tensor:
+    p = torch.arange(ctx)
+    return block_table_row.long()[p // PAGE] * PAGE + (p % PAGE)
+
+
+def paged_decode_attn_ref64(q, kcache, vcache, block_table, ctx_lens, scale):
+    """Gathers slots through the block table; softmax in fp64.  -> [B,H,D] f64"""
+    q, kcache, vcache = q.cpu(), kcache.cpu(), vcache.cpu()
+    B, H, D = q.shape
+    P, _, Hk, _ = kcache.shape
+    rep = H // Hk
+    kf = kcache.double().reshape(P * PAGE, Hk, D)
+    vf = vcache.double().reshape(P * PAGE, Hk, D)
+    out = torch.empty(B, H, D, dtype=torch.float64)
+    for b in range(B):
+        sl = slots_of(block_table[b].cpu(), int(ctx_lens[b]))
+        kk, vv = kf[sl], vf[sl]
+        for h in range(H):
+            s = (kk[:, h // rep] @ q[b, h].double()) * scale
+            out[b, h] = torch.softmax(s, dim=0) @ vv[:, h // rep]
+    return out
+
+
+def plant_spike(case: dict, b: int, h: int, p_star: int):
+    """K[p*] = 16 q[b,h] on head h's kv head (in a CLONE of the K cache).
+    Returns (kcache_new, gap, v_row): gap is the fp64 score distance from p*
+    to the best other position (inf when ctx == 1); v_row = V[p*] for the
+    kv head, which the kernel must return bit for bit when gap is large:
+    every other weight is <= exp(-gap), far below half an fp32 ulp."""
+    q, kc, vc = case["q"], case["kcache"].clone(), case["vcache"]
+    H = q.shape[1]
+    P, _, Hk, D = kc.shape
+    kvh = h // (H // Hk)
+    ctx = int(case["ctx_lens"][b])
+    sl = slots_of(case["block_table"][b], ctx)
+    kflat = kc.view(P * PAGE, Hk, D)
+    kflat[sl[p_star], kvh] = (q[b, h].float() * 16.0).to(BF16)
+    s = (kflat[sl, kvh].double() @ q[b, h].double()) * case["scale"]
+    others = torch.cat([s[:p_star], s[p_star + 1:]])
+    gap = float(s[p_star] - others.max()) if others.numel() else float("inf")
+    return kc, gap, vc.view(P * PAGE, Hk, D)[sl[p_star], kvh].clone()
+
+
+def attn_bound(vcache: torch.Tensor) -> float:
+    """2^-8 max|V|.  The output o is a convex combination of V rows, so
+    |o| <= max|V| and half a bf16 ulp of o is <= 2^-8 |o|, reaching
+    2^-8 max|V| only if |o| == max|V| is a power of two; what is left covers
+    the fp32 softmax error (~1e-5 relative at |score| <= 100)."""
+    return U_BF16_OUT * float(vcache.double().abs().max())
+
+
+# --------------------------------------------------------------------------
+# RoPE
+# --------------------------------------------------------------------------
+def rope_ref64(x: torch.Tensor, cos_sin: torch.Tensor, positions: torch.Tensor):
+    """Rotate-half RoPE.  x [T,H,D] bf16, cos_sin [max_pos, D] f32 (the table
+    the kernel reads).  Returns (out64, bound64) with
+    bound = 2^-8 (|a c| + |b s|) per output element."""
+    xd = x.cpu().double()
+    half = xd.shape[-1] // 2
+    cs = cos_sin.cpu().double()[positions.cpu().long()]
+    c, s = cs[:, :half].unsqueeze(1), cs[:, half:].unsqueeze(1)
+    x1, x2 = xd[..., :half], xd[..., half:]
+    out = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+    bound = U_BF16_OUT * torch.cat([(x1 * c).abs() + (x2 * s).abs(),
+                                    (x2 * c).abs() + (x1 * s).abs()], dim=-1)
+    return out, bound
+
+
+SENTINEL = 1.5  # non-zero cache pre-fill: a stray write of anything else shows
+
+
+# --------------------------------------------------------------------------
+# Sampling
+# --------------------------------------------------------------------------
+def argmax_ref_rows(logits: torch.Tensor) -> torch.Tensor:
+    """Lowest index of the maximum over non-NaN entries; 0 if there is none."""
+    x = logits.cpu().double()
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+    mx = x.max(dim=1, keepdim=True).values
+    first = (x == mx).to(torch.int64).argmax(dim=1)  # first True
+    return first.to(torch.int32)
+
+
+def target_logprob_ref64(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    lp = torch.log_softmax(logits.cpu().double(), dim=-1)
+    return lp.gather(1, targets.cpu().long().unsqueeze(1)).squeeze(1)
+
+
+def argmax_edge_rows(gen, vocab: int):
+    """Rows of edge cases for argmax_rows at one vocab size.
+    Returns (logits [R, vocab] bf16, names)."""
+    rows, names = [], []
+
+    def add(name, r):
+        rows.append(r)
+        names.append(name)
+
+    add("random", rand_bf16(gen, vocab))
+    r = rand_bf16(gen, vocab); r[0] = 50.0
+    add("max_first", r)
+    r = rand_bf16(gen, vocab); r[vocab - 1] = 50.0
+    add("max_last", r)
+    add("all_equal", torch.full((vocab,), 0.75, dtype=BF16))
+    add("all_neg_inf", torch.full((vocab,), float("-inf"), dtype=BF16))
+    r = rand_bf16(gen, vocab)
+    r[torch.arange(0, vocab, 3)] = float("nan")   # index 0 is NaN
+    add("nan_ignored", r)
+    r = rand_bf16(gen, vocab); r[vocab - 1] = 50.0; r[0] = float("nan")
+    add("nan_first_max_last", r)
+    add("all_nan", torch.full((vocab,), float("nan"), dtype=BF16))
+    a, b = 8 * 255 + 3, 8 * 256
+    if b < vocab:
+        # equal maxima in thread 255's first pass and thread 0's second pass
+        r = rand_bf16(gen, vocab); r[a] = 50.0; r[b] = 50.0
+        add("tie_across_passes", r)
+    return torch.stack(rows), names
+
+
+def target_logprob_edge_rows(gen, vocab: int):
+    """Rows of edge cases for target_logprob.  Returns (logits, targets, names);
+    every row has a finite target, so every output must be finite."""
+    rows, tgts, names = [], [], []
+
+    def add(name, r, t):
+        rows.append(r)
+        tgts.append(t)
+        names.append(name)
+
+    add("random", rand_bf16(gen, vocab), vocab // 2)
+    add("x30_tgt_first", (torch.randn(vocab, generator=gen) * 30).to(BF16), 0)
+    add("x30_tgt_last", (torch.randn(vocab, generator=gen) * 30).to(BF16), vocab - 1)
+    # -inf over the first 16-byte vector (a thread's FIRST element is -inf)
+    r = rand_bf16(gen, vocab)
+    r[:min(8, vocab - 1)] = float("-inf")
+    add("neg_inf_head", r, vocab - 1)
+    r = (torch.randn(vocab, generator=gen) * 30).to(BF16)
+    mask = torch.rand(vocab, generator=gen) < 0.5
+    mask[:min(8, vocab - 1)] = True
+    mask[vocab - 1] = False
+    r[mask] = float("-inf")
+    add("neg_inf_half_x30", r, vocab - 1)
+    r = torch.full((vocab,), float("-inf"), dtype=BF16); r[vocab // 2] = 3.0
+    add("single_finite", r, vocab // 2)
+    r = rand_bf16(gen, vocab); r[0] = float("-inf")
+    add("neg_inf_first_tgt_1", r, 1)
+    return torch.stack(rows), torch.tensor(tgts, dtype=torch.int32), names
+
+
+# --------------------------------------------------------------------------
+# Check drivers shared by the CPU (ops.* fallbacks) and GPU (HIP kernels)
+# test files.  ``fn(x, *wargs) -> [M, N] bf16`` is the op under test.
+# --------------------------------------------------------------------------
+def _to(dev, ts):
+    return tuple(t.to(dev) for t in ts)
+
+
+def check_gemv_onehot(fn, kind, Ms, Ns, K, dev, gen):
+    """Row m of x is one-hot at column k_m: C[m, :] == W[:, k_m] bit for bit
+    (0 * w and the sums of zeros are exact; W[:, k] x 1 is a bf16 value)."""
+    for N in Ns:
+        wargs, w64 = make_weights(kind, gen, N, K, "random")
+        wdev = _to(dev, wargs)
+        for M in Ms:
+            for cols in onehot_calls(M, K):
+                got = fn(onehot_x(cols, K).to(dev), *wdev)
+                exp = exact_bf16(w64[:, cols].t().contiguous())
+                assert_bits_equal(got, exp, f"{kind} one-hot M={M} N={N} K={K} cols={cols}")
+
+
+def check_gemv_int(fn, kind, Ms, Ns, K, dev, gen):
+    """Small-integer data: every fp32 partial sum is an exactly representable
+    integer multiple of the smallest scale, whatever the summation order, so
+    the output equals bf16_rne(exact sum) bit for bit."""
+    for N in Ns:
+        wargs, w64 = make_weights(kind, gen, N, K, "int")
+        wdev = _to(dev, wargs)
+        for M in Ms:
+            x = int_x(gen, M, K)
+            # premise: |any partial sum| <= sum|x||w| < 2^24 units of 2^-3
+            assert float(gemv_abs_dot(x, w64).max()) * 8 < 2 ** 24
+            got = fn(x.to(dev), *wdev)
+            exp = exact_bf16(gemv_ref64(x, w64))
+            assert_bits_equal(got, exp, f"{kind} integer M={M} N={N} K={K}")
+
+
+def check_gemv_random(fn, kind, Ms, Ns, K, dev, gen, mode="random"):
+    for N in Ns:
+        wargs, w64 = make_weights(kind, gen, N, K, mode)
+        wdev = _to(dev, wargs)
+        for M in Ms:
+            x = rand_bf16(gen, M, K)
+            got = fn(x.to(dev), *wdev)
+            ref = gemv_ref64(x, w64)
+            assert_within(got, ref, gemv_bound(ref, gemv_abs_dot(x, w64), K),
+                          f"{kind} random M={M} N={N} K={K}")
+
+
+def check_gemv_norm(fn, Ms, Ns, K, dev, gen, with_res, onehot=False, eps=1e-5,
+                    fro_tol=None):
+    """fn(x, res, normw, b, eps) -> (C, res_out).  Elementwise bound with 2K
+    in place of K (the extra b*normw and t*bw product roundings, the
+    sum-of-squares error and rsqrt all fit in the second K); res_out must be
+    bit-equal.  ``fro_tol`` replaces the elementwise bound by a relative
+    Frobenius bound (CPU fallback, which rounds t and y to bf16)."""
+    for N in Ns:
+        b = rand_bf16(gen, N, K)
+        normw = rand_bf16(gen, K)
+        for M in Ms:
+            calls = ([onehot_x(c, K) for c in onehot_calls(M, K)] if onehot
+                     else [rand_bf16(gen, M, K)])
+            for x in calls:
+                res = rand_bf16(gen, M, K) if with_res else None
+                if onehot and with_res:
+                    x = x * 0.5   # x + res is exactly one-hot
+                    res = x.clone()
+                c, res_out = fn(x.to(dev), res.to(dev) if res is not None else None,
+                                normw.to(dev), b.to(dev), eps)
+                c64, ro, absdot = gemv_norm_ref64(x, res, normw, b, eps)
+                what = f"gemv_norm M={M} N={N} K={K} res={with_res} onehot={onehot}"
+                assert_bits_equal(res_out, ro, what + " res_out")
+                if fro_tol is not None:
+                    assert rel_fro(c, c64) <= fro_tol, what
+                else:
+                    assert_within(c, c64, gemv_bound(c64, absdot, K, kfactor=2), what)
+
+
+def check_swiglu_onehot(fn, Ns, K, dev, gen):
+    """fn(gateup [1,2K], w [N,K]).  Activation == 32 e_k exactly, so the
+    output is 32 W[:, k] bit for bit."""
+    for N in Ns:
+        w = rand_bf16(gen, N, K)
+        wd = w.to(dev)
+        for k in probe_columns(K):
+            got = fn(swiglu_onehot_gateup(gen, k, K).to(dev), wd)
+            exp = exact_bf16(32.0 * w[:, k].double()).unsqueeze(0)
+            assert_bits_equal(got, exp, f"swiglu one-hot N={N} K={K} k={k}")
+
+
+SWIGLU_FRO_TOL = 2.0 ** -8
+
+
+def check_swiglu_random(fn, Ns, K, dev, gen):
+    """The activation is rounded to bf16 before the dot, so the check is the
+    relative Frobenius error: two independent bf16 roundings in quadrature
+    give ~2e-3 (measured on MI355X: 1.8e-3 .. 2.6e-3, and up to 3.4e-3 at
+    N=8 where only 8 outputs are averaged); a dropped 512-slot at K=5120
+    gives ~0.3.  Bound 2^-8 = 3.9e-3."""
+    for N in Ns:
+        w = rand_bf16(gen, N, K)
+        gu = rand_bf16(gen, 1, 2 * K)
+        got = fn(gu.to(dev), w.to(dev))
+        ref = swiglu_ref64(gu) @ w.double().t()
+        r = rel_fro(got, ref)
+        print(f"swiglu random N={N} K={K}: rel_fro={r:.3e}")
+        assert r <= SWIGLU_FRO_TOL, f"swiglu random N={N} K={K}: rel_fro={r:.3e}"
+
+
+def check_paged_onehot(fn, ctx, dev, gen, H=2, min_gap=60.0):
+    """fn(q, kcache, vcache, block_table, ctx_lens, scale) -> [B,H,D]."""
+    case = make_paged_case(gen, [ctx], H, H)
+    d = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in case.items()}
+    for i, p in enumerate(probe_positions(ctx)):
+        h = i % H
+        kc, gap, v_row = plant_spike(case, 0, h, p)
+        assert gap >= min_gap, f"generator: score gap {gap} < {min_gap}"
+        got = fn(d["q"], kc.to(dev), d["vcache"], d["block_table"], d["ctx_lens"],
+                 case["scale"])
+        assert_bits_equal(got[0, h], v_row, f"paged one-hot ctx={ctx} p*={p} head={h}")
+
+
+def check_paged_random(fn, ctxs, H, Hk, dev, gen, mode):
+    """mode: 'diffuse' | 'peaked' (q x 4, outputs O(1)) | 'late_spike'
+    (K[ctx-3] *= 8: alpha << 1 in a later pass and a rescale in the merge)."""
+    case = make_paged_case(gen, ctxs, H, Hk, qscale=4.0 if mode == "peaked" else 1.0)
+    if mode == "late_spike":
+        P, _, _, D = case["kcache"].shape
+        kflat = case["kcache"].view(P * PAGE, Hk, D)
+        for b, ctx in enumerate(ctxs):
+            if ctx >= 3:
+                s = slots_of(case["block_table"][b], ctx)[ctx - 3]
+                kflat[s] = (kflat[s].float() * 8).to(BF16)
+    d = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in case.items()}
+    got = fn(d["q"], d["kcache"], d["vcache"], d["block_table"], d["ctx_lens"],
+             case["scale"])
+    ref = paged_decode_attn_ref64(case["q"], case["kcache"], case["vcache"],
+                                  case["block_table"], case["ctx_lens"], case["scale"])
+    assert_within(got, ref, torch.tensor(attn_bound(case["vcache"]), dtype=torch.float64),
+                  f"paged random ctxs={ctxs} H={H} Hk={Hk} {mode}")
+
+
+def check_rope_kv_append(fn, Hq, Hk, D, dev, gen, rope_tables, P=8, max_pos=300):
+    """fn(qkv, cos_sin, positions, slot, kcache_flat, vcache_flat, Hq, Hk, D) -> q."""
+    pos = torch.tensor([0, 1, 17, max_pos - 1, 0], dtype=torch.int32)
+    slot = torch.tensor([0, P * PAGE - 1, 5, 21, 64], dtype=torch.int32)
+    B = pos.numel()
+    qs, kvs = Hq * D, Hk * D
+    qkv = rand_bf16(gen, B, qs + 2 * kvs)
+    cs = rope_tables(max_pos, D, 500000.0)
+    kc = torch.full((P * PAGE, Hk, D), SENTINEL, dtype=BF16)
+    vc = torch.full((P * PAGE, Hk, D), SENTINEL, dtype=BF16)
+    kcd, vcd = kc.clone().to(dev), vc.clone().to(dev)  # .to() aliases on the CPU
+    q = fn(qkv.to(dev), cs.to(dev), pos.to(dev), slot.to(dev), kcd, vcd, Hq, Hk, D)
+    q_in = qkv[:, :qs].reshape(B, Hq, D)
+    k_in = qkv[:, qs:qs + kvs].reshape(B, Hk, D)
+    v_in = qkv[:, qs + kvs:].reshape(B, Hk, D)
+    q64, qb = rope_ref64(q_in, cs, pos)
+    k64, kb = rope_ref64(k_in, cs, pos)
+    what = f"rope_kv_append Hq={Hq} Hk={Hk} D={D}"
+    assert_within(q, q64, qb, what + " q")
+    sl = slot.long()
+    assert_within(kcd.cpu()[sl], k64, kb, what + " k")
+    assert_bits_equal(vcd.cpu()[sl], v_in.contiguous(), what + " v rows")
+    for i in (pos == 0).nonzero().flatten().tolist():   # cos = 1, sin = 0
+        assert_bits_equal(q.cpu()[i], q_in[i].contiguous(), what + " q at position 0")
+        assert_bits_equal(kcd.cpu()[sl[i]], k_in[i].contiguous(), what + " k at position 0")
+    untouched = torch.ones(P * PAGE, dtype=torch.bool)
+    untouched[sl] = False
+    assert_bits_equal(kcd.cpu()[untouched], kc[untouched], what + " stray K-cache write")
+    assert_bits_equal(vcd.cpu()[untouched], vc[untouched], what + " stray V-cache write")
+
+
+def check_rope_scatter(fn, Hq, Hk, D, dev, gen, rope_tables, B=2, S=64, max_pos=300):
+    """fn(qkv, cos_sin, positions, Hq, Hk, D, B, S) -> (q [B,Hq,S,D], k [B,Hk,S,D])."""
+    T = B * S
+    pos = torch.randint(0, max_pos, (T,), generator=gen).to(torch.int32)
+    pos[0], pos[1], pos[T - 1] = 0, max_pos - 1, 0
+    qs, kvs = Hq * D, Hk * D
+    qkv = rand_bf16(gen, T, qs + 2 * kvs)
+    cs = rope_tables(max_pos, D, 500000.0)
+    qo, ko = fn(qkv.to(dev), cs.to(dev), pos.to(dev), Hq, Hk, D, B, S)
+    q_in = qkv[:, :qs].reshape(T, Hq, D)
+    k_in = qkv[:, qs:qs + kvs].reshape(T, Hk, D)
+    what = f"rope_scatter Hq={Hq} Hk={Hk} D={D}"
+    for got, x_in, Hh, nm in ((qo, q_in, Hq, "q"), (ko, k_in, Hk, "k")):
+        assert tuple(got.shape) == (B, Hh, S, D)
+        got_t = got.cpu().permute(0, 2, 1, 3).reshape(T, Hh, D)  # token-major
+        r64, bnd = rope_ref64(x_in, cs, pos)
+        assert_within(got_t, r64, bnd, f"{what} {nm}")
+        z = (pos == 0).nonzero().flatten()
+        assert_bits_equal(got_t[z].contiguous(), x_in[z].contiguous(),
+                          f"{what} {nm} at position 0")
+
+
+def check_argmax(fn, vocab, dev, gen, single_rows=False):
+    """fn(logits [R, vocab] bf16) -> int32 [R]."""
+    logits, names = argmax_edge_rows(gen, vocab)
+    exp = argmax_ref_rows(logits)
+    if single_rows:
+        got = torch.cat([fn(logits[i:i + 1].contiguous().to(dev)).cpu()
+                         for i in range(logits.shape[0])])
+    else:
+        got = fn(logits.to(dev)).cpu()
+    assert got.dtype == torch.int32
+    for i, nm in enumerate(names):
+        g, e = int(got[i]), int(exp[i])
+        assert 0 <= g < vocab, f"argmax vocab={vocab} {nm}: {g} out of range"
+        assert g == e, f"argmax vocab={vocab} {nm}: got {g} expected {e}"
+    fixed = {"max_first": 0, "max_last": vocab - 1, "all_equal": 0, "all_neg_inf": 0,
+             "all_nan": 0, "nan_first_max_last": vocab - 1,
+             "tie_across_passes": 8 * 255 + 3}
+    for i, nm in enumerate(names):
+        if nm in fixed:
+            assert int(exp[i]) == fixed[nm], f"oracle: {nm}"
+
+
+def check_target_logprob(fn, vocab, dev, gen, tol=1e-3):
+    """fn(logits, targets) -> f32 [R]; atol = rtol = 1e-3, all finite."""
+    logits, tgt, names = target_logprob_edge_rows(gen, vocab)
+    got = fn(logits.to(dev), tgt.to(dev)).cpu().double()
+    ref = target_logprob_ref64(logits, tgt)
+    assert bool(torch.isfinite(ref).all()), "oracle: finite targets only"
+    for i, nm in enumerate(names):
+        g, r = float(got[i]), float(ref[i])
+        assert math.isfinite(g), f"target_logprob vocab={vocab} {nm}: got {g} (ref {r})"
+        assert abs(g - r) <= tol + tol * abs(r), \
+            f"target_logprob vocab={vocab} {nm}: got {g} ref {r}"
+    # a row with nothing finite has no distribution: NaN, as torch gives
+    allneg = torch.full((1, vocab), float("-inf"), dtype=BF16)
+    out = fn(allneg.to(dev), torch.zeros(1, dtype=torch.int32).to(dev))
+    assert bool(torch.isnan(out).all())
