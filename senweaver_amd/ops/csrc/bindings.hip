@@ -174,6 +174,8 @@ torch::Tensor vt_from_qkv(torch::Tensor qkv, int64_t Hq, int64_t Hk, int64_t D,
   check_bf16(qkv, "qkv");
   const long long ld = qkv.size(1);
   TORCH_CHECK(qkv.size(0) == B * S && ld >= (Hq + 2 * Hk) * D);
+  // the kernel reads 16-byte chunks at (row * ld + head * D + 8 c)
+  TORCH_CHECK(ld % 8 == 0 && D % 8 == 0, "vt_from_qkv: row length and D must be multiples of 8");
   auto vt = torch::empty({B, Hk, D, S}, qkv.options());
   const long long v_off = (Hq + Hk) * D;
   transpose_v_kernel<<<dim3((unsigned)((S + 31) / 32), (unsigned)((D + 63) / 64),
@@ -466,6 +468,16 @@ std::vector<torch::Tensor> gemv_norm_bt(torch::Tensor x, c10::optional<torch::Te
 }
 
 // ---------------- Flash attention prefill ----------------
+// The kernels index k and vt with q's batch / sequence strides, so a k or vt
+// of another shape would be read at the wrong rows (or out of bounds).
+static void check_attn_kv(const torch::Tensor& k, const torch::Tensor& vt,
+                          int B, int S, int D, const char* op) {
+  TORCH_CHECK(k.dim() == 4 && vt.dim() == 4, op, ": k and vt must be 4-D");
+  TORCH_CHECK(k.size(0) == B && k.size(2) == S && k.size(3) == D, op,
+              ": k must be [B,Hk,S,D] matching q's B, S and D");
+  TORCH_CHECK(vt.size(0) == B, op, ": vt batch must match q");
+}
+
 torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
                        double scale) {
   check_bf16(q, "q");
@@ -477,6 +489,7 @@ torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   TORCH_CHECK(S % 64 == 0, "S must be padded to 64");
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S, "vt must be [B,Hk,D,S]");
   TORCH_CHECK(H % Hk == 0);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd");
   auto o = torch::empty_like(q);
   attn_fwd_bf16_kernel<<<dim3(S / 64, H, B), dim3(256), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(o), B, H, Hk, S, (float)scale);
@@ -494,6 +507,7 @@ torch::Tensor attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   const int Hk = k.size(1);
   TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd_v2");
   auto ot = torch::empty({B, H, D, S}, q.options());
   attn_fwd_v2_kernel<<<dim3(S / 128, H, B), dim3(256), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);
@@ -511,6 +525,7 @@ torch::Tensor attn_fwd_v3(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   const int Hk = k.size(1);
   TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd_v3");
   auto ot = torch::empty({B, H, D, S}, q.options());
   attn_fwd_v3_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);
@@ -537,6 +552,7 @@ torch::Tensor attn_fwd_v4(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   const int Hk = k.size(1);
   TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd_v4");
   auto ot = torch::empty({B, H, D, S}, q.options());
   const bool four_wave = (var == 16 || var == 18);  // QBLK 128, 256 threads
   dim3 grid(four_wave ? (S + 127) / 128 : (S + 255) / 256, H, B);
@@ -576,6 +592,7 @@ torch::Tensor attn_fwd_v5(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   const int Hk = k.size(1);
   TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd_v5");
   auto ot = torch::empty({B, H, D, S}, q.options());
   attn_fwd_v4_15_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);

@@ -1,8 +1,9 @@
-"""fp64 oracles, input generators and error bounds for the decode kernels.
+"""fp64 oracles, input generators and error bounds for the decode kernels
+and the prefill attention kernels.
 
-Helper module for test_kernel_oracles_cpu.py and test_decode_edges_gpu.py
-(no tests live here).  Every oracle takes the SAME bf16 / uint8 tensors the
-kernel gets, upcasts with ``.double()`` and computes in plain torch on the
+Helper module for test_kernel_oracles_cpu.py, test_decode_edges_gpu.py and
+test_prefill_edges_gpu.py (no tests live here).  Every oracle takes the
+SAME bf16 / uint8 tensors the kernel gets, upcasts with ``.double()`` and computes in plain torch on the
 CPU, so the only error in an oracle is fp64 rounding (~1e-16 relative).
 
 Bounds are derived from the number formats, never from kernel output:
@@ -647,3 +648,340 @@ def check_target_logprob(fn, vocab, dev, gen, tol=1e-3):
     allneg = torch.full((1, vocab), float("-inf"), dtype=BF16)
     out = fn(allneg.to(dev), torch.zeros(1, dtype=torch.int32).to(dev))
     assert bool(torch.isnan(out).all())
+
+
+# --------------------------------------------------------------------------
+# Prefill attention (causal, GQA, D = 128).  The op under test is
+# ``fn(q [B,H,S,D], k [B,Hk,S,D], vt [B,Hk,D,S], scale) -> O^T [B,H,D,S]``.
+# --------------------------------------------------------------------------
+PREFILL_D = 128
+PREFILL_SCALE = 1.0 / math.sqrt(PREFILL_D)
+V_FLOOR = 2.0 ** -6          # pointer cases: every |v| is at least this
+POINTER_MIN_GAP = 60.0       # nats between the target and every other key
+SCORE_LOG2_MAX = 300.0       # premise of prefill_bound: |score * log2 e|
+PREFILL_S_MAX = 2048         # premise of prefill_bound
+DEFER_THRESHOLD = 8.0        # nats; the kernels' documented defer-max rule
+POINTER_MAPS = ("diag", "first", "tile_first", "tile_prev_last",
+                "wave_prev_last", "random")
+PREFILL_MODES = ("diffuse", "peaked", "early_spike",
+                 "stair+3", "stair+7", "stair+9", "stair-7")
+
+
+def kv_head_of(H: int, Hk: int) -> torch.Tensor:
+    """Query head -> kv head (GQA: consecutive groups of H/Hk heads)."""
+    assert H % Hk == 0
+    return torch.arange(H) // (H // Hk)
+
+
+def _scores64(q, k, scale, b, heads) -> torch.Tensor:
+    """Unmasked fp64 scores [len(heads), S, S] of batch b."""
+    kvh = kv_head_of(q.shape[1], k.shape[1])[heads]
+    return (q[b, heads].double() @ k[b, kvh].double().transpose(-1, -2)) * scale
+
+
+def attn_prefill_ref64(q, k, v, scale) -> torch.Tensor:
+    """Causal GQA attention on the bf16 values as given, softmax in fp64.
+    q [B,H,S,D], k/v [B,Hk,S,D] -> [B,H,S,D] fp64."""
+    q, k, v = q.cpu(), k.cpu(), v.cpu()
+    B, H, S, D = q.shape
+    kvh = kv_head_of(H, k.shape[1])
+    hidden = torch.ones(S, S, dtype=torch.bool).triu(1)   # key j > row i
+    out = torch.empty(B, H, S, D, dtype=torch.float64)
+    heads = torch.arange(H)
+    for b in range(B):
+        s = _scores64(q, k, scale, b, heads).masked_fill(hidden, float("-inf"))
+        out[b] = torch.softmax(s, dim=-1) @ v[b, kvh].double()
+    return out
+
+
+def max_abs_score_log2(q, k, scale) -> float:
+    """max |score| * log2(e) over ALL (row, key) pairs, masked ones included
+    (the kernels compute a masked score before they discard it)."""
+    q, k = q.cpu(), k.cpu()
+    B, H = q.shape[:2]
+    m = 0.0
+    for b in range(B):
+        for h0 in range(0, H, 64):
+            heads = torch.arange(h0, min(H, h0 + 64))
+            m = max(m, float(_scores64(q, k, scale, b, heads).abs().max()))
+    return m * math.log2(math.e)
+
+
+def prefill_bound(v: torch.Tensor) -> float:
+    """(2^-8 + 2^-12) max|V|: elementwise bound on |kernel - fp64 reference|
+    for |score * log2 e| <= 300 and S <= 2048 (both asserted by the checks).
+
+    The kernels compute p_j = exp(s_j - m) in fp32, sum l = sum p_j from the
+    UNROUNDED p_j, round p_j to bf16 for the PV MFMA, accumulate in fp32 and
+    round o = (sum p_j v_j) / l to bf16.
+
+    * 2^-9 max|V| for P rounded to bf16: each weight moves by a relative
+      delta_j, the output by sum_j delta_j p_j v_j / l.  Half a bf16 ulp is
+      between 2^-9 and 2^-8 of the value, so the strict worst case (every
+      delta_j at its maximum, all with the sign of v_j, every |v_j| at
+      max|V|) would be 2^-8 max|V|; the term used here holds once the
+      delta_j are not all adversarial, which the measured ratios (printed
+      per case) confirm.  A weight of exactly 1 (one dominating key) rounds
+      without error.
+    * 2^-9 |o| <= 2^-9 max|V| for the bf16 rounding of the output (|o| <=
+      max|V|: a convex combination), with the same remark.
+    * 2^-12 max|V| for the fp32 terms: the exponent's argument is off by at
+      most 300 * 2^-23 relative (product and subtraction roundings at
+      magnitude <= 300), the fp32 sums by S * 2^-24 <= 2^-13 relative, and
+      v_exp_f32 / rcp by about an ulp each — together < 2^-12 relative.
+    """
+    return (2.0 ** -8 + 2.0 ** -12) * float(v.double().abs().max())
+
+
+def clamp_v(v: torch.Tensor) -> torch.Tensor:
+    """Every |v| pushed up to at least 2^-6 (sign kept, zero -> +2^-6): the
+    pointer cases compare bits, and a zero element would let the e^-gap
+    dust of the other keys decide its sign and value."""
+    floor = torch.where(v < 0, -V_FLOOR, V_FLOOR).to(v.dtype)
+    return torch.where(v.abs() < V_FLOOR, floor, v)
+
+
+def pointer_targets(tmap: str, S: int, gen: torch.Generator) -> torch.Tensor:
+    """Target key t(i) <= i for every row i (int64 [S])."""
+    i = torch.arange(S)
+    if tmap == "diag":
+        t = i.clone()
+    elif tmap == "first":
+        t = torch.zeros(S, dtype=torch.int64)
+    elif tmap == "tile_first":
+        t = 64 * (i // 64)
+    elif tmap == "tile_prev_last":
+        t = (64 * (i // 64) - 1).clamp(min=0)
+    elif tmap == "wave_prev_last":
+        t = (32 * (i // 32) - 1).clamp(min=0)
+    elif tmap == "random":
+        t = (torch.rand(S, generator=gen, dtype=torch.float64) * (i + 1)).long()
+        t = torch.minimum(t, i)
+    else:
+        raise ValueError(tmap)
+    assert bool((t <= i).all()) and bool((t >= 0).all())
+    return t
+
+
+def _sign_codes(gen, *shape) -> torch.Tensor:
+    return (torch.randint(0, 2, shape, generator=gen) * 2 - 1).to(BF16)
+
+
+def make_pointer_case(gen, B, H, Hk, S, tmap) -> dict:
+    """Pointer attention: K[j] = c_j in {+-1}^128, Q[i] = 16 c_t(i), codes and
+    V drawn per (batch, kv head).  Every score is an exact integer times
+    scale; the target scores 16 * 128 * scale = 181.02 nats.  ``expected`` is
+    V[t(i)] per row, [B,H,S,D]."""
+    D = PREFILL_D
+    codes = _sign_codes(gen, B, Hk, S, D)
+    t = pointer_targets(tmap, S, gen)
+    kvh = kv_head_of(H, Hk)
+    q = (codes[:, kvh][:, :, t].float() * 16.0).to(BF16)
+    v = clamp_v(rand_bf16(gen, B, Hk, S, D))
+    assert float(v.abs().min()) >= V_FLOOR
+    if B * Hk > 1:   # a wrong batch / head index must land on other bits
+        flat = v.reshape(B * Hk, -1)
+        assert not any(torch.equal(flat[0], flat[i]) for i in range(1, B * Hk))
+    return dict(q=q, k=codes, v=v, vt=v.transpose(-1, -2).contiguous(),
+                scale=PREFILL_SCALE, t=t, expected=v[:, kvh][:, :, t].contiguous())
+
+
+def pointer_min_gap(q, k, t, scale) -> float:
+    """min over EVERY row of (score of the target - best other score), in
+    fp64, the other keys taken over the whole sequence (not only the visible
+    ones — the stricter reading)."""
+    B, H, S, _ = q.shape
+    idx = t.view(1, S, 1)
+    gap = float("inf")
+    for b in range(B):
+        for h0 in range(0, H, 64):
+            heads = torch.arange(h0, min(H, h0 + 64))
+            s = _scores64(q, k, scale, b, heads)
+            ix = idx.expand(len(heads), S, 1)
+            tgt = s.gather(2, ix).squeeze(2)
+            other = s.scatter(2, ix, float("-inf")).max(dim=2).values
+            gap = min(gap, float((tgt - other).min()))
+    return gap
+
+
+def check_pointer(fn, B, H, Hk, S, tmap, dev, gen, prep=None):
+    """Every row must return V[t(i)] BIT FOR BIT: the target's weight is
+    exp(0) = 1, every other weight <= e^-60 (1e-26, against half an fp32 ulp
+    of 6e-8), so l = 1, 1/l = 1 and the accumulated dust is < 2^-24 |v| for
+    |v| >= 2^-6.  This holds across defer-max: before the target's tile the
+    weights are <= e^8 relative to a stale max, and the rescale at the
+    target multiplies them down to <= e^-gap.  ``prep`` maps the device q
+    and k before the call (non-contiguous views)."""
+    c = make_pointer_case(gen, B, H, Hk, S, tmap)
+    gap = pointer_min_gap(c["q"], c["k"], c["t"], c["scale"])
+    assert gap >= POINTER_MIN_GAP, f"generator: score gap {gap} < {POINTER_MIN_GAP}"
+    q, k = c["q"].to(dev), c["k"].to(dev)
+    if prep is not None:
+        q, k = prep(q), prep(k)
+    got = fn(q, k, c["vt"].to(dev), c["scale"])
+    what = f"pointer {tmap} B={B} H={H} Hk={Hk} S={S}"
+    assert tuple(got.shape) == (B, H, PREFILL_D, S), f"{what}: not O^T [B,H,D,S]"
+    assert_bits_equal(got, c["expected"].transpose(-1, -2).contiguous(), what)
+    return gap
+
+
+def make_decoy_case(gen, B, H, Hk, S) -> dict:
+    """Q[i] = 16 c_{i+1} for i < S-1 (the last row points at itself): the
+    strongest key of every row is the first MASKED one."""
+    c = make_pointer_case(gen, B, H, Hk, S, "diag")
+    t = torch.arange(S)
+    t[:-1] += 1
+    kvh = kv_head_of(H, Hk)
+    c["q"] = (c["k"][:, kvh][:, :, t].float() * 16.0).to(BF16)
+    c["t"] = t
+    del c["expected"]
+    return c
+
+
+def check_future_decoy(fn, B, H, Hk, S, dev, gen):
+    """The mask must hide a key that would dominate.  Expectation: the fp64
+    softmax over keys <= i within prefill_bound; row 0 == V[0] bit for bit.
+    Premises, every row: the decoy beats every visible key by >= 60 nats,
+    and (rows 1 .. S-2) the reference is further than 4 bounds from V[i+1]
+    in at least one element, so a leak cannot pass."""
+    c = make_decoy_case(gen, B, H, Hk, S)
+    q, k, v = c["q"], c["k"], c["v"]
+    kvh = kv_head_of(H, Hk)
+    assert S <= PREFILL_S_MAX and max_abs_score_log2(q, k, c["scale"]) <= SCORE_LOG2_MAX
+    hidden = torch.ones(S, S, dtype=torch.bool).triu(1)
+    for b in range(B):
+        s = _scores64(q, k, c["scale"], b, torch.arange(H))
+        decoy = s.diagonal(offset=1, dim1=1, dim2=2)                  # [H, S-1]
+        vis = s.masked_fill(hidden, float("-inf")).max(dim=2).values  # [H, S]
+        lead = float((decoy - vis[:, :-1]).min())
+        assert lead >= POINTER_MIN_GAP, f"generator: decoy leads by only {lead}"
+    ref = attn_prefill_ref64(q, k, v, c["scale"])
+    bound = prefill_bound(v)
+    leak = v[:, kvh].double()[:, :, 2:]                               # V[i+1], i = 1..S-2
+    sep = (ref[:, :, 1:S - 1] - leak).abs().max(dim=-1).values
+    assert float(sep.min()) > 4 * bound, "generator: a leak would pass"
+    got = fn(q.to(dev), k.to(dev), c["vt"].to(dev), c["scale"])
+    what = f"future decoy B={B} H={H} Hk={Hk} S={S}"
+    assert tuple(got.shape) == (B, H, PREFILL_D, S), f"{what}: not O^T [B,H,D,S]"
+    ratio = err_ratio(got, ref.transpose(-1, -2), bound)
+    print(f"{what}: max err / bound = {ratio:.3f}")
+    assert_within(got, ref.transpose(-1, -2), bound, what)
+    assert_bits_equal(got[:, :, :, 0], v[:, kvh][:, :, 0], what + " row 0")
+    return ratio
+
+
+def err_ratio(got, ref64, bound: float) -> float:
+    return float((got.detach().cpu().double() - ref64).abs().max()) / bound
+
+
+def make_prefill_case(gen, mode, B, H, Hk, S) -> dict:
+    """Random / staircase inputs.  'diffuse': randn.  'peaked': q x 4.
+    'early_spike': K[100] x 8.  'stair<step>': Q[i] = u (one sign vector per
+    (batch, kv head)), K[j] = kappa_j u + randn with kappa_j =
+    bf16(step * (j // 64) / sqrt(128)), so the scores climb (or fall) by
+    ``step`` nats per 64-key tile with N(0,1) noise on top."""
+    D = PREFILL_D
+    kvh = kv_head_of(H, Hk)
+    v = rand_bf16(gen, B, Hk, S, D)
+    if mode.startswith("stair"):
+        step = float(mode[len("stair"):])
+        u = _sign_codes(gen, B, Hk, 1, D)
+        q = u[:, kvh].expand(B, H, S, D).contiguous()
+        kappa = (step * (torch.arange(S) // 64).double() / math.sqrt(D)).to(BF16)
+        k = (kappa.float().view(1, 1, S, 1) * u.float()
+             + torch.randn(B, Hk, S, D, generator=gen)).to(BF16)
+    else:
+        q = torch.randn(B, H, S, D, generator=gen)
+        q = (q * 4.0 if mode == "peaked" else q).to(BF16)
+        k = rand_bf16(gen, B, Hk, S, D)
+        if mode == "early_spike":
+            assert S > 100
+            k[:, :, 100] = (k[:, :, 100].float() * 8.0).to(BF16)
+        assert mode in ("diffuse", "peaked", "early_spike"), mode
+    return dict(q=q, k=k, v=v, vt=v.transpose(-1, -2).contiguous(), scale=PREFILL_SCALE)
+
+
+def stair_tile_maxes(q, k, scale, b=0, h=0) -> torch.Tensor:
+    """fp64 max score of each 64-key tile as the LAST row sees it (all keys
+    visible; every row of a staircase case has the same q)."""
+    s = _scores64(q, k, scale, b, torch.tensor([h]))[0, -1]
+    return s.view(-1, 64).max(dim=1).values
+
+
+def defer_pattern(tile_max: torch.Tensor, thr: float = DEFER_THRESHOLD) -> str:
+    """The defer-max rule replayed in fp64 on a row's tile maxima: 'D' where
+    a tile stays within ``thr`` nats of the running max (max kept stale),
+    'R' where it rescales.  The first tile always rescales (from -inf)."""
+    m, out = float("-inf"), []
+    for t in tile_max.tolist():
+        if t - m <= thr:
+            out.append("D")
+        else:
+            out.append("R")
+            m = max(m, t)
+    return "".join(out)
+
+
+def assert_stair_premises(q, k, scale, mode):
+    """Measured in fp64 for every (batch, head): the mean step per tile is
+    within 1 nat of the nominal one and every single step within 2.5 (the
+    max of 64 N(0,1) draws has a standard deviation of about 0.5, a step is
+    the difference of two, the mean step (M_last - M_0) / (tiles - 1));
+    the defer rule then goes through the regime the case is meant for."""
+    step = float(mode[len("stair"):])
+    B, H = q.shape[:2]
+    for b in range(B):
+        for h in range(H):
+            M = stair_tile_maxes(q, k, scale, b, h)
+            d = M[1:] - M[:-1]
+            assert abs(float(d.mean()) - step) <= 1.0, f"{mode}: mean step {float(d.mean())}"
+            assert float((d - step).abs().max()) <= 2.5, f"{mode}: steps {d.tolist()}"
+            pat = defer_pattern(M)[1:]
+            if step == 3:      # defer, defer, rescale: each under 8, the sum over
+                # (three tiles, S = 192, end before the rescale)
+                assert "DDR" in pat if len(pat) >= 3 else pat == "DD", pat
+            elif step == 7:    # defer and rescale alternate; never two defers
+                assert "DR" in pat and "DD" not in pat, pat
+                assert len(pat) < 3 or "RD" in pat, pat
+            elif step == 9:    # rescales back to back (a step that the noise
+                # brings under 8 still defers now and then, never twice)
+                assert "DD" not in pat and pat.count("R") >= pat.count("D"), pat
+                assert len(pat) < 4 or "RR" in pat, pat
+            elif step == -7:   # every tile defers against tile 0's max
+                assert pat == "D" * len(pat), pat
+            else:
+                raise ValueError(mode)
+
+
+def check_prefill_random(fn, mode, B, H, Hk, S, dev, gen):
+    """fn against attn_prefill_ref64 within prefill_bound, elementwise; row 0
+    (one visible key: p = 1, l = 1) must equal V[0] bit for bit.  Returns the
+    measured max error / bound (also printed)."""
+    c = make_prefill_case(gen, mode, B, H, Hk, S)
+    q, k, v = c["q"], c["k"], c["v"]
+    assert S <= PREFILL_S_MAX
+    smax = max_abs_score_log2(q, k, c["scale"])
+    assert smax <= SCORE_LOG2_MAX, f"generator: |score log2 e| = {smax}"
+    if mode.startswith("stair"):
+        assert_stair_premises(q, k, c["scale"], mode)
+    ref = attn_prefill_ref64(q, k, v, c["scale"]).transpose(-1, -2)
+    bound = prefill_bound(v)
+    got = fn(q.to(dev), k.to(dev), c["vt"].to(dev), c["scale"])
+    what = f"prefill {mode} B={B} H={H} Hk={Hk} S={S}"
+    assert tuple(got.shape) == (B, H, PREFILL_D, S), f"{what}: not O^T [B,H,D,S]"
+    ratio = err_ratio(got, ref, bound)
+    print(f"{what}: max err / bound = {ratio:.3f}")
+    assert_within(got, ref, bound, what)
+    assert_bits_equal(got[:, :, :, 0], v[:, kv_head_of(H, Hk)][:, :, 0], what + " row 0")
+    return ratio
+
+
+def check_vt_from_qkv(fn, B, S, Hq, Hk, D, dev, gen, extra_cols=0):
+    """fn(qkv [B*S, (Hq+2Hk)*D + extra_cols], Hq, Hk, D, B, S) -> V^T
+    [B,Hk,D,S], a pure copy: bit-equal to permute(0,2,3,1).contiguous()."""
+    ld = (Hq + 2 * Hk) * D + extra_cols
+    qkv = rand_bf16(gen, B * S, ld)
+    exp = qkv[:, (Hq + Hk) * D:(Hq + 2 * Hk) * D].reshape(B, S, Hk, D)
+    exp = exp.permute(0, 2, 3, 1).contiguous()
+    got = fn(qkv.to(dev), Hq, Hk, D, B, S)
+    assert_bits_equal(got, exp, f"vt_from_qkv B={B} S={S} Hq={Hq} Hk={Hk} D={D} ld={ld}")

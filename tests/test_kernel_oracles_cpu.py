@@ -1,4 +1,5 @@
-"""CPU checks of the decode-kernel oracles (tests/kernel_oracles.py).
+"""CPU checks of the decode-kernel and prefill-attention oracles
+(tests/kernel_oracles.py).
 
 Three things are established without a GPU:
 1. each fp64 oracle agrees with the existing fp32 reference in
@@ -6,7 +7,9 @@ Three things are established without a GPU:
 2. every input generator satisfies the condition its GPU test relies on
    (score gap, integer-sum magnitude, power-of-two scales, exact
    representability of the bit-exact expectations);
-3. the ops.* CPU fallbacks pass the same edge cases the GPU kernels get.
+3. the ops.* CPU fallbacks pass the same edge cases the GPU kernels get;
+4. every check rejects operators that are wrong in the way it is meant to
+   catch (and accepts a legitimately different one).
 """
 
 import math
@@ -381,3 +384,303 @@ def test_cpu_argmax_fallback(gen, vocab):
 @pytest.mark.parametrize("vocab", [8, 512, 1000, 2048])
 def test_cpu_target_logprob_fallback(gen, vocab):
     ko.check_target_logprob(ops.target_logprob, vocab, CPU, gen)
+
+
+# ==========================================================================
+# Prefill attention: oracle, generator premises, CPU fallbacks and the wrong
+# operators each check has to reject (test_prefill_edges_gpu.py runs the
+# same checks on the HIP kernels).
+# ==========================================================================
+PREFILL_SEED = 20241      # the seed of test_prefill_edges_gpu.py's generator
+HEAD_CONFIGS = [(1, 1, 1), (2, 4, 2), (1, 6, 2)]
+ALL_POINTER_S = [64, 128, 192, 256, 320, 384, 512, 640]
+
+
+@pytest.fixture
+def pgen():
+    return torch.Generator().manual_seed(PREFILL_SEED)
+
+
+def _ops_attn_fwd(q, k, vt, s):
+    return ops.attn_fwd(q, k, None, s, vt=vt).transpose(-1, -2).contiguous()
+
+
+def attn_variant(mask="causal", kv_map="div", batch0=False, transposed=True,
+                 p_bf16=False, tiled=None):
+    """An fp64 attention operator built from the reference with one property
+    switched.  mask: 'causal' | 'ge' (kv >= q hidden) | 'plus1' (kv > q+1
+    hidden) | 'skip32' (the first row of every 32-row group sees its whole
+    64-key tile).  kv_map: 'div' (h // rep) | 'mod' (h % Hk).  p_bf16: P
+    rounded to bf16 AND l summed from the rounded values.  tiled: None, or
+    64-key online softmax with the 8-nat defer rule, 'ok' or 'bug' (deferred
+    tiles add exp(s - m - 8) to O while l sums exp(s - m))."""
+    def fn(q, k, vt, scale):
+        q, k, v = q.cpu(), k.cpu(), vt.cpu().transpose(-1, -2)
+        B, H, S, D = q.shape
+        Hk = k.shape[1]
+        i, j = torch.arange(S).view(S, 1), torch.arange(S).view(1, S)
+        hidden = {"causal": j > i, "ge": j >= i, "plus1": j > i + 1,
+                  "skip32": (j > i) & ~((i % 32 == 0) & (j < 64 * (i // 64) + 64))}[mask]
+        kvh = torch.arange(H) // (H // Hk) if kv_map == "div" else torch.arange(H) % Hk
+        out = torch.empty(B, H, S, D, dtype=torch.float64)
+        for b in range(B):
+            bb = 0 if batch0 else b
+            s = (q[b].double() @ k[bb, kvh].double().transpose(-1, -2)) * scale
+            s = s.masked_fill(hidden, float("-inf"))
+            vv = v[bb, kvh].double()
+            if tiled is None:
+                p = torch.exp(s - s.max(dim=-1, keepdim=True).values)
+                if p_bf16:
+                    p = p.to(ko.BF16).double()
+                out[b] = (p @ vv) / p.sum(dim=-1, keepdim=True)
+                continue
+            m = torch.full((H, S, 1), float("-inf"), dtype=torch.float64)
+            l = torch.zeros(H, S, 1, dtype=torch.float64)
+            o = torch.zeros(H, S, D, dtype=torch.float64)
+            for t0 in range(0, S, 64):
+                st = s[:, :, t0:t0 + 64]
+                tm = st.max(dim=-1, keepdim=True).values
+                defer = (tm - m) <= ko.DEFER_THRESHOLD      # NaN / +inf: False
+                m_new = torch.where(defer, m, torch.maximum(m, tm))
+                alpha = torch.where(m == float("-inf"), torch.zeros_like(m),
+                                    torch.exp(m - m_new))
+                p = torch.exp(st - m_new)
+                l = l * alpha + p.sum(dim=-1, keepdim=True)
+                if tiled == "bug":
+                    p = torch.where(defer, p * math.exp(-8.0), p)
+                o = o * alpha + p @ vv[:, t0:t0 + 64]
+                m = m_new
+            out[b] = o / l
+        o16 = out.to(ko.BF16)
+        return o16.transpose(-1, -2).contiguous() if transposed else o16
+    return fn
+
+
+# ---------------- oracle agreement ----------------
+def test_attn_prefill_ref64_matches_fp32_reference(gen):
+    for B, H, Hk, S in [(2, 4, 2, 192), (1, 6, 2, 128)]:
+        c = ko.make_prefill_case(gen, "peaked", B, H, Hk, S)
+        r64 = ko.attn_prefill_ref64(c["q"], c["k"], c["v"], c["scale"])
+        r32 = ref.attn_fwd_ref(c["q"], c["k"], c["v"], c["scale"], causal=True)
+        # the fp32 reference rounds its output to bf16 and nothing else
+        ko.assert_within(r32, r64, ko.U_BF16_OUT * r64.abs() + 1e-5)
+        # row 0 sees one key
+        kvh = ko.kv_head_of(H, Hk)
+        assert torch.equal(r64[:, :, 0], c["v"][:, kvh][:, :, 0].double())
+    # and the tiled fp64 formulation (with defers) is the same function
+    c = ko.make_prefill_case(gen, "stair+3", 1, 4, 2, 384)
+    r64 = ko.attn_prefill_ref64(c["q"], c["k"], c["v"], c["scale"])
+    got = attn_variant(tiled="ok")(c["q"], c["k"], c["vt"], c["scale"])
+    ko.assert_within(got.transpose(-1, -2), r64, ko.U_BF16_OUT * r64.abs() + 1e-12)
+
+
+# ---------------- generator premises ----------------
+def test_pointer_targets_hit_the_edges():
+    g = torch.Generator().manual_seed(0)
+    i = torch.arange(320)
+    assert torch.equal(ko.pointer_targets("diag", 320, g), i)
+    assert int(ko.pointer_targets("first", 320, g).max()) == 0
+    t = ko.pointer_targets("tile_first", 320, g)
+    assert [int(t[x]) for x in (0, 63, 64, 127, 319)] == [0, 0, 64, 64, 256]
+    t = ko.pointer_targets("tile_prev_last", 320, g)
+    assert [int(t[x]) for x in (0, 63, 64, 127, 128, 319)] == [0, 0, 63, 63, 127, 255]
+    t = ko.pointer_targets("wave_prev_last", 320, g)   # kv0 + 63 == q0 - 1 + 32 k
+    assert [int(t[x]) for x in (0, 31, 32, 63, 64, 96, 319)] == [0, 0, 31, 31, 63, 95, 287]
+    t = ko.pointer_targets("random", 320, g)
+    assert bool((t <= i).all()) and int(t[0]) == 0 and len(set(t.tolist())) > 100
+
+
+@pytest.mark.parametrize("S", ALL_POINTER_S)
+def test_pointer_premises_every_row(pgen, S):
+    """Gap >= 60 nats for EVERY row (pointer_min_gap takes the minimum over
+    all rows, the other keys over the whole sequence), V clamped, integer
+    scores, distinct V per (batch, kv head) — for every map and head
+    configuration, drawn as the GPU test draws them."""
+    for tmap in ko.POINTER_MAPS:
+        g = torch.Generator().manual_seed(PREFILL_SEED)
+        for B, H, Hk in HEAD_CONFIGS:
+            c = ko.make_pointer_case(g, B, H, Hk, S, tmap)
+            gap = ko.pointer_min_gap(c["q"], c["k"], c["t"], c["scale"])
+            assert gap >= ko.POINTER_MIN_GAP, (S, tmap, gap)
+            assert float(c["v"].abs().min()) >= ko.V_FLOOR
+            assert set(c["k"].unique().tolist()) == {-1.0, 1.0}
+            assert set(c["q"].unique().tolist()) == {-16.0, 16.0}
+            kvh = ko.kv_head_of(H, Hk)
+            tgt = (c["q"].double() * c["k"][:, kvh][:, :, c["t"]].double()).sum(-1)
+            assert bool((tgt == 16.0 * 128).all())          # 181.02 nats
+            assert c["expected"].shape == (B, H, S, ko.PREFILL_D)
+
+
+def test_pointer_premises_dispatch_shapes(pgen):
+    for B, H, Hk in [(1, 512, 512), (1, 511, 511), (2, 256, 64)]:
+        for tmap in ("diag", "random"):
+            g = torch.Generator().manual_seed(PREFILL_SEED)
+            c = ko.make_pointer_case(g, B, H, Hk, 256, tmap)
+            assert ko.pointer_min_gap(c["q"], c["k"], c["t"], c["scale"]) >= ko.POINTER_MIN_GAP
+
+
+def test_clamp_v():
+    v = torch.tensor([0.0, -0.0, 2.0 ** -7, -(2.0 ** -7), 2.0 ** -6, -3.0, 0.5]).to(ko.BF16)
+    got = ko.clamp_v(v)
+    assert got.tolist() == [2.0 ** -6, 2.0 ** -6, 2.0 ** -6, -(2.0 ** -6), 2.0 ** -6, -3.0, 0.5]
+
+
+@pytest.mark.parametrize("S", ALL_POINTER_S)
+def test_decoy_premises(pgen, S):
+    """Run on the exact oracle: the check asserts its own premises (decoy
+    lead >= 60 nats, separation from V[i+1] > 4 bounds for every row >= 1,
+    score range) before it looks at the operator's output."""
+    ratio = ko.check_future_decoy(attn_variant(), 2, 4, 2, S, CPU, pgen)
+    assert ratio <= 1.0   # bf16 output rounding only: half an ulp <= 2^-8 |o|
+
+
+@pytest.mark.parametrize("S", [192, 320, 384, 640])
+@pytest.mark.parametrize("mode", ko.PREFILL_MODES)
+def test_random_case_premises(pgen, mode, S):
+    c = ko.make_prefill_case(pgen, mode, 1, 4, 2, S)
+    assert ko.max_abs_score_log2(c["q"], c["k"], c["scale"]) <= ko.SCORE_LOG2_MAX
+    if mode.startswith("stair"):
+        ko.assert_stair_premises(c["q"], c["k"], c["scale"], mode)
+
+
+def test_defer_pattern_regimes():
+    step = lambda d, n: torch.arange(n, dtype=torch.float64) * d
+    assert ko.defer_pattern(step(3.0, 7)) == "RDDRDDR"
+    assert ko.defer_pattern(step(7.0, 6)) == "RDRDRD"
+    assert ko.defer_pattern(step(9.0, 5)) == "RRRRR"
+    assert ko.defer_pattern(step(-7.0, 5)) == "RDDDD"
+    assert ko.defer_pattern(torch.tensor([0.0, 8.0, 8.5, 16.5])) == "RDRD"
+
+
+# ---------------- CPU fallbacks, smallest S of each list ----------------
+@pytest.mark.parametrize("tmap", ko.POINTER_MAPS)
+@pytest.mark.parametrize("S", [64, 128])
+def test_cpu_prefill_pointer(pgen, S, tmap):
+    for B, H, Hk in HEAD_CONFIGS:
+        ko.check_pointer(ops.attn_fwd_t, B, H, Hk, S, tmap, CPU, pgen)
+        ko.check_pointer(_ops_attn_fwd, B, H, Hk, S, tmap, CPU, pgen)
+
+
+@pytest.mark.parametrize("S", [64, 128])
+def test_cpu_prefill_future_decoy(pgen, S):
+    ko.check_future_decoy(ops.attn_fwd_t, 2, 4, 2, S, CPU, pgen)
+    ko.check_future_decoy(_ops_attn_fwd, 2, 4, 2, S, CPU, pgen)
+
+
+@pytest.mark.parametrize("mode", ko.PREFILL_MODES)
+@pytest.mark.parametrize("S", [192, 384])
+def test_cpu_prefill_vs_fp64(pgen, S, mode):
+    ko.check_prefill_random(ops.attn_fwd_t, mode, 1, 4, 2, S, CPU, pgen)
+
+
+def test_cpu_prefill_dispatch_shapes_and_views(pgen):
+    """The public ops at a dispatch shape and on permuted [B,S,H,D] views
+    (on the CPU both run the fp32 reference)."""
+    def bshd_view(t):
+        view = t.permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)
+        assert not view.is_contiguous()
+        return view
+
+    ko.check_pointer(ops.attn_fwd_t, 2, 256, 64, 256, "random", CPU, pgen)
+    for fn, S in ((ops.attn_fwd_t, 256), (_ops_attn_fwd, 192)):
+        for tmap in ("diag", "random"):
+            ko.check_pointer(fn, 2, 4, 2, S, tmap, CPU, pgen, prep=bshd_view)
+
+
+@pytest.mark.parametrize("S", [1, 7, 8, 31, 33, 100])
+def test_cpu_vt_from_qkv(pgen, S):
+    for D in (64, 128):
+        for Hq, Hk in [(1, 1), (4, 2), (6, 2)]:
+            for B in (1, 2):
+                ko.check_vt_from_qkv(ops.vt_from_qkv, B, S, Hq, Hk, D, CPU, pgen)
+    ko.check_vt_from_qkv(ops.vt_from_qkv, 2, S, 4, 2, 128, CPU, pgen, extra_cols=8)
+
+    def drops_last_column(qkv, Hq, Hk, D, B, S_):
+        vt = ops.vt_from_qkv(qkv, Hq, Hk, D, B, S_).clone()
+        vt[..., S_ - 1] = 0
+        return vt
+
+    with pytest.raises(AssertionError):
+        ko.check_vt_from_qkv(drops_last_column, 2, S, 4, 2, 128, CPU, pgen)
+
+
+# ---------------- wrong operators ----------------
+def _rejected(check, *args):
+    with pytest.raises(AssertionError) as e:
+        check(*args)
+    assert not str(e.value).startswith("generator"), e.value   # not a premise
+
+
+def test_exact_variant_passes_every_check(pgen):
+    """The operator the wrong ones are cut from passes, so each rejection
+    below is due to the one switched property."""
+    for fn in (attn_variant(), attn_variant(tiled="ok")):
+        for B, H, Hk in HEAD_CONFIGS:
+            for tmap in ko.POINTER_MAPS:
+                ko.check_pointer(fn, B, H, Hk, 128, tmap, CPU, pgen)
+        ko.check_future_decoy(fn, 2, 4, 2, 128, CPU, pgen)
+        for mode in ko.PREFILL_MODES:
+            ko.check_prefill_random(fn, mode, 1, 4, 2, 384, CPU, pgen)
+
+
+@pytest.mark.parametrize("S", [64, 128, 384])
+def test_mask_ge_rejected_by_pointer_diag(pgen, S):
+    _rejected(ko.check_pointer, attn_variant(mask="ge"), 1, 1, 1, S, "diag", CPU, pgen)
+
+
+@pytest.mark.parametrize("S", [64, 128, 384])
+def test_mask_plus1_rejected_by_future_decoy(pgen, S):
+    bad = attn_variant(mask="plus1")
+    _rejected(ko.check_future_decoy, bad, 2, 4, 2, S, CPU, pgen)
+    # no pointer map can see it: the extra key is 60 nats down
+    for tmap in ko.POINTER_MAPS:
+        ko.check_pointer(bad, 1, 1, 1, S, tmap, CPU, pgen)
+
+
+@pytest.mark.parametrize("S", [64, 128, 384])
+def test_mask_skipped_on_wave_first_row_rejected_by_future_decoy(pgen, S):
+    _rejected(ko.check_future_decoy, attn_variant(mask="skip32"), 2, 4, 2, S, CPU, pgen)
+
+
+@pytest.mark.parametrize("B,H,Hk", [(2, 4, 2), (1, 6, 2)])
+def test_kv_head_mod_rejected_by_pointer(pgen, B, H, Hk):
+    bad = attn_variant(kv_map="mod")
+    for tmap in ko.POINTER_MAPS:
+        _rejected(ko.check_pointer, bad, B, H, Hk, 128, tmap, CPU, pgen)
+    ko.check_pointer(bad, 1, 1, 1, 128, "diag", CPU, pgen)   # one head: same map
+
+
+def test_batch0_rejected_by_pointer(pgen):
+    bad = attn_variant(batch0=True)
+    for tmap in ko.POINTER_MAPS:
+        _rejected(ko.check_pointer, bad, 2, 4, 2, 128, tmap, CPU, pgen)
+
+
+def test_untransposed_output_rejected(pgen):
+    bad = attn_variant(transposed=False)
+    _rejected(ko.check_pointer, bad, 1, 1, 1, 128, "diag", CPU, pgen)     # on value
+    _rejected(ko.check_pointer, bad, 1, 1, 1, 64, "diag", CPU, pgen)      # on shape
+    _rejected(ko.check_prefill_random, bad, "diffuse", 1, 4, 2, 384, CPU, pgen)
+    _rejected(ko.check_future_decoy, bad, 2, 4, 2, 128, CPU, pgen)
+
+
+def test_p_rounded_to_bf16_stays_within_the_bound(pgen):
+    """P in bf16 with l summed from the ROUNDED weights is a legitimate
+    design (its error is of the size the bound grants): it must pass."""
+    ok = attn_variant(p_bf16=True)
+    for S in (192, 384):
+        for mode in ko.PREFILL_MODES:
+            ko.check_prefill_random(ok, mode, 1, 4, 2, S, CPU, pgen)
+    ko.check_future_decoy(ok, 2, 4, 2, 128, CPU, pgen)
+    for tmap in ko.POINTER_MAPS:
+        ko.check_pointer(ok, 2, 4, 2, 128, tmap, CPU, pgen)
+
+
+@pytest.mark.parametrize("mode", ["stair+3", "stair+7"])
+@pytest.mark.parametrize("S", [192, 384, 640])
+def test_uncompensated_defer_rejected_by_staircase(pgen, S, mode):
+    """Deferred tiles weighted exp(s - m - 8) in O but exp(s - m) in l.  The
+    rising staircases put the row's heaviest keys into deferred tiles.  (On
+    'stair-7' the deferred tiles hold e^-7 of the weight, so the same slip
+    moves the output by 1e-3 max|V|: no bf16-level bound can see it there.)"""
+    _rejected(ko.check_prefill_random, attn_variant(tiled="bug"), mode, 1, 4, 2, S, CPU, pgen)
