@@ -27,6 +27,7 @@ from ..apo.schema import RolloutResult
 from ..models.config import ModelConfig, get_config
 from ..models.llama import LlamaModel
 from .kvcache import PAGE_SIZE, PagedKVCache
+from .prefix_plan import plan_from_lcp
 from . import tokenizer as tok
 
 
@@ -37,7 +38,8 @@ def _pad64(n: int) -> int:
 
 class LlamaBackend:
     def __init__(self, config: ModelConfig | str = "llama-3-8b", device: Optional[str] = None,
-                 seed: int = 0, max_seq: int = 2048, micro_batch: int = 8, tp=None, quant: str = "bf16") -> None:
+                 seed: int = 0, max_seq: int = 2048, micro_batch: int = 8, tp=None, quant: str = "bf16",
+                 prefix_pack: bool = True) -> None:
         if isinstance(config, str):
             config = get_config(config)
         if device is None:
@@ -48,6 +50,10 @@ class LlamaBackend:
         self.tokenizer = tok.for_vocab(config.vocab_size)
         self.max_seq = min(max_seq, config.max_position)
         self.micro_batch = micro_batch
+        # prefix-packed prefill: a token prefix shared by consecutive rows of
+        # a microbatch (the candidate prompt, in score_batch's candidate-major
+        # order) is computed once instead of once per rollout
+        self.prefix_pack = prefix_pack
 
     # ------------------------------------------------------------------
     # Sequence building
@@ -155,13 +161,31 @@ class LlamaBackend:
             # microbatches back)
             m = mask.clone()
             m[:, 0] = False  # position 0 has no predictor
+            lcp = None
+            if self.prefix_pack and B > 1:
+                # common prefix of each row with the previous one, enqueued
+                # ahead of nonzero() so its sync covers this too
+                same = (tokens[1:] == tokens[:-1]).to(torch.int32)
+                lcp = same.cumprod(dim=1).sum(dim=1)
             flat_pos = m.reshape(-1).nonzero(as_tuple=False).squeeze(1)
             if flat_pos.numel() == 0:
                 return torch.zeros(B, dtype=torch.float32, device=tokens.device)
-            hidden = self.model.prefill(tokens)  # [B, S, H]
+            plan = None
+            if lcp is not None:
+                plan = plan_from_lcp([0] + lcp.tolist(), S)
             # p >= 1 within every sequence (position 0 masked off above), so
             # flat_pos - 1 stays inside the same sequence's rows
-            rows = hidden.reshape(B * S, -1)[flat_pos - 1]
+            if plan is not None and not plan.is_identity:
+                hidden = self.model.prefill_packed(tokens, plan)  # [Tp, H]
+                skip, base, owner = self.model.plan_tensors(plan)[:3]
+                prev = flat_pos - 1
+                b = torch.div(prev, S, rounding_mode="floor")
+                s = prev - b * S
+                src = torch.where(s < skip[b], owner[b].long(), b)
+                rows = hidden[base[src] + s]
+            else:
+                hidden = self.model.prefill(tokens)  # [B, S, H]
+                rows = hidden.reshape(B * S, -1)[flat_pos - 1]
             logits = self.model.logits(rows)
             targets = tokens.reshape(-1)[flat_pos].to(torch.int32)
             lp = ops.target_logprob(logits, targets)

@@ -1,11 +1,13 @@
 """Llama backbone on the senweaver_amd gfx950 kernel library.
 
 Replaces the reference's remote LLM providers (sendLLMMessage.impl.ts's 20
-HTTPS backends) with a local model whose hot path is entirely hand-written
-HIP: MFMA GEMM for every projection, fused residual+RMSNorm, table-driven
-RoPE, flash prefill attention, paged decode attention, SwiGLU, and fused
-logit reductions.  PyTorch supplies tensor storage, reshapes/transposes and
-the embedding gather only.
+HTTPS backends) with a local model whose fused and shape-special ops are
+hand-written HIP: fused residual+RMSNorm, table-driven RoPE, flash prefill
+attention, paged decode attention, SwiGLU, decode GEMV, fp8/mxfp8 GEMMs and
+fused logit reductions.  Plain bf16 prefill projections go to hipBLASLt
+through ``ops.gemm_bt`` (it measured faster than the in-repo tiled MFMA GEMM
+at those shapes; SENWEAVER_GEMM=hip forces the in-repo kernel).  PyTorch
+supplies tensor storage, reshapes/transposes and the embedding gather.
 
 Weights are random-init bf16 (no network access for checkpoints — bench data
 is declared synthetic).
@@ -232,7 +234,90 @@ class LlamaModel:
         h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
         return h.reshape(B, S, c.hidden_size)
 
-    def _ffn(self, h: torch.Tensor, L: dict) -> torch.Tensor:
+    # ------------------------------------------------------------------
+    # Prefix-packed prefill: tokens [B, S] + plan -> final hidden states of
+    # the Tp PACKED rows [Tp, H] (engine/prefix_plan.py).  A token prefix
+    # shared by consecutive rows is computed once, in the group leader's
+    # rows; everything row-wise (GEMMs, norms, SwiGLU, TP all-reduces) runs
+    # on Tp rows instead of B*S.  Only rope_scatter, the V^T transpose and
+    # the attention epilogue know the mapping: Q/K/V^T are expanded to the
+    # ordinary [B, H, S, D] layouts (prefix broadcast to every member) and
+    # attention writes straight into one packed O^T [Hq*D, Tp].
+    # ------------------------------------------------------------------
+    def plan_tensors(self, plan):
+        """Device copies of a plan (skip, base, owner int32 [B]; positions
+        int32 [Tp]; flat token index int64 [Tp]), cached per layout: the
+        scorer sees the same layout for every candidate of a step."""
+        cache = self.__dict__.setdefault("_plan_cache", {})
+        key = (plan.S, plan.owner, plan.skip)
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= 64:
+                cache.clear()
+            pos = torch.cat([torch.arange(plan.skip[b], plan.S)
+                             for b in range(plan.B)])
+            row = torch.repeat_interleave(
+                torch.arange(plan.B),
+                torch.tensor([plan.S - s for s in plan.skip]))
+            hit = tuple(t.to(self.device) for t in (
+                torch.tensor(plan.skip, dtype=torch.int32),
+                torch.tensor(plan.base, dtype=torch.int32),
+                torch.tensor(plan.owner, dtype=torch.int32),
+                pos.to(torch.int32), row * plan.S + pos))
+            cache[key] = hit
+        return hit
+
+    def prefill_packed(self, tokens: torch.Tensor, plan) -> torch.Tensor:
+        c = self.config
+        B, S = tokens.shape
+        skip, base, owner, positions, flat_idx = self.plan_tensors(plan)
+        Tp = plan.Tp
+        if plan.is_identity or (self.device.type == "cuda"
+                                and (S % 128 != 0 or S < 256)):
+            # nothing shared, or a shape the packed attention kernel does not
+            # take: the unpacked path, handed back in packed-row order
+            return self.prefill(tokens).reshape(B * S, -1)[flat_idx]
+
+        hidden = self.embed[tokens.reshape(B * S)[flat_idx]]  # [Tp, H]
+        residual = None
+        for L in self.layers:
+            if residual is None:
+                residual = hidden.clone()
+                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
+            else:
+                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
+            qkv = self._linear(h, L, "qkv")  # [Tp, local q+2kv]
+            qb, kb = ops.rope_scatter_qkv_packed(
+                qkv, self.cos_sin, positions, self.local_heads,
+                self.local_kv_heads, c.head_dim, B, S, skip, base, owner)
+            vt = ops.vt_from_qkv_packed(qkv, self.local_heads,
+                                        self.local_kv_heads, c.head_dim, B, S,
+                                        skip, base, owner)
+            ot = ops.attn_fwd_t_packed(qb, kb, vt, self.scale, skip, base, Tp,
+                                       flat_idx)
+            if self.quant == "bf16":
+                # one o_proj GEMM off the transposed view (hipBLASLt takes
+                # the transposed A natively)
+                o = torch.matmul(ot.t(), L["o"].t())
+            else:
+                o = self._linear(ot.t().contiguous(), L, "o")
+            self.tp.all_reduce_(o)
+            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
+            # The down projection stays at the unpacked row count.  Its
+            # N = hidden is only 16 tile columns wide, so B*S rows are a whole
+            # number of waves over the CUs while Tp rows are not, and the
+            # library's stream-K kernel then loses more than the rows save:
+            # measured at Llama-3-8B, 605 us at M=8192 against 901 (M=6848)
+            # and 652 (M=7040) — profiles/prefix_packed_breakdown.txt.  It
+            # also keeps every row's sum order what the unpacked path has.
+            hidden = self._ffn(h, L, down_rows=B * S)
+        return ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
+
+    def _ffn(self, h: torch.Tensor, L: dict,
+             down_rows: Optional[int] = None) -> torch.Tensor:
+        """``down_rows`` (dense bf16 only): run the down-projection GEMM at
+        this many rows (zero rows appended to the activation, their outputs
+        dropped) instead of h's row count."""
         c = self.config
         if c.num_experts == 0:
             gateup = self._linear(h, L, "gateup")
@@ -240,6 +325,9 @@ class LlamaModel:
                     and gateup.is_cuda
                     and os.environ.get("SENWEAVER_SWIGLU_FUSE", "0") == "1"):
                 out = ops.swiglu_gemv(gateup, L["down"])
+            elif self.quant == "bf16" and down_rows is not None:
+                act = ops.swiglu(gateup, down_rows)
+                out = self._linear(act, L, "down")[:gateup.shape[0]]
             else:
                 act = ops.swiglu(gateup)
                 out = self._linear(act, L, "down")

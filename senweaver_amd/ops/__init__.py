@@ -163,7 +163,62 @@ def vt_from_qkv(qkv: torch.Tensor, Hq: int, Hk: int, D: int, B: int, S: int
     return v.permute(0, 2, 3, 1).contiguous()
 
 
-def swiglu(gateup: torch.Tensor) -> torch.Tensor:
+# ---- prefix-packed prefill (engine/prefix_plan.py; csrc/README.md) ----
+# qkv holds Tp packed rows; skip/base/owner are int32 [B] plan arrays on the
+# tensor's device.  Q, K and V^T come out in the ordinary [B, H, S, D] /
+# [B, Hk, D, S] layouts with the shared prefix broadcast to every member.
+
+def rope_scatter_qkv_packed(qkv: torch.Tensor, cos_sin, positions, Hq: int,
+                            Hk: int, D: int, B: int, S: int, skip, base, owner):
+    """rope_scatter_qkv reading packed rows; ``positions`` is per PACKED row."""
+    if _on_gpu(qkv):
+        qo, ko = hip_ext().rope_scatter_qkv_packed(
+            qkv.contiguous(), cos_sin, positions.to(torch.int32), Hq, Hk, D,
+            B, S, skip, base, owner)
+        return qo, ko
+    src = ref.packed_src_rows_ref(B, S, skip, base, owner).reshape(-1)
+    return rope_scatter_qkv(qkv[src], cos_sin, positions[src], Hq, Hk, D, B, S)
+
+
+def vt_from_qkv_packed(qkv: torch.Tensor, Hq: int, Hk: int, D: int, B: int,
+                       S: int, skip, base, owner) -> torch.Tensor:
+    """vt_from_qkv reading packed rows."""
+    if _on_gpu(qkv):
+        return hip_ext().vt_from_qkv_packed(qkv.contiguous(), Hq, Hk, D, B, S,
+                                            skip, base, owner)
+    src = ref.packed_src_rows_ref(B, S, skip, base, owner).reshape(-1)
+    return vt_from_qkv(qkv[src], Hq, Hk, D, B, S)
+
+
+def attn_fwd_t_packed(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
+                      scale: float, skip, base, Tp: int, flat_idx) -> torch.Tensor:
+    """Causal GQA attention to ONE packed O^T [H*D, Tp]: row (b, s >= skip[b])
+    lands in column base[b] + s; query rows below skip[b] are the leader's.
+    ``flat_idx`` [Tp] is b*S + s of every packed row.  S % 128 == 0 and
+    S >= 256 on GPU.
+
+    Same kernel choice as attn_fwd_t, so packing never changes which
+    attention numerics a shape gets: where the grid fills the chip, the
+    packed v5 kernel (prefix blocks skipped, packed store in the epilogue);
+    on tiny grids v2 on all rows, its columns then gathered."""
+    B, H, S, D = q.shape
+    if _on_gpu(q) and _ATTN_IMPL != "v2" and ((S + 255) // 256) * B * H >= 512:
+        return hip_ext().attn_fwd_v5_packed(q.contiguous(), k.contiguous(),
+                                            vt.contiguous(), scale, skip, base,
+                                            Tp)
+    ot = attn_fwd_t(q, k, vt, scale)  # [B,H,D,S]
+    return ot.permute(1, 2, 0, 3).reshape(H * D, B * S).index_select(1, flat_idx)
+
+
+def swiglu(gateup: torch.Tensor, out_rows: Optional[int] = None) -> torch.Tensor:
+    """silu(gate) * up.  With ``out_rows`` > rows (2-D input) the result has
+    out_rows rows, zero past the input's: the next GEMM can run at a row
+    count of the caller's choice without a pad copy."""
+    if out_rows is not None and out_rows > gateup.shape[0]:
+        if _on_gpu(gateup):
+            return hip_ext().swiglu_padded(gateup.contiguous(), out_rows)
+        act = ref.swiglu_ref(gateup)
+        return torch.nn.functional.pad(act, (0, 0, 0, out_rows - act.shape[0]))
     if _on_gpu(gateup):
         return hip_ext().swiglu(gateup.contiguous())
     return ref.swiglu_ref(gateup)

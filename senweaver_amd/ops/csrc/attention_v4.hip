@@ -84,15 +84,28 @@ static __device__ __forceinline__ float v4_exp2(float x) {
   return r;
 }
 
+// PACK (prefix-packed prefill, non-TEPI only): Q/K/V^T are indexed as usual,
+// but query rows below skip[b] belong to the group leader and are not
+// recomputed — a block entirely below skip[b] exits before any LDS traffic
+// or barrier, and the epilogue stores row q of batch row b to column
+// base[b] + q of ONE 2-D O^T [H*D, Tp] (row h*D + d) instead of [B,H,D,S].
 template <int STAGE, int DEFER, int DIET = 0, int SPLIT = 0,
-          int NT = 512, int TEPI = 0>
+          int NT = 512, int TEPI = 0, int PACK = 0>
 static __device__ __forceinline__ void attn4_body(
     const ushort* __restrict__ Q, const ushort* __restrict__ K,
     const ushort* __restrict__ VT, ushort* __restrict__ OT, int B, int H,
-    int Hk, int S, float scale) {
+    int Hk, int S, float scale, const int* __restrict__ pk_skip = nullptr,
+    const int* __restrict__ pk_base = nullptr, int Tp = 0) {
   const int qb = gridDim.x - 1 - blockIdx.x;  // heaviest-first
   const int h = blockIdx.y;
   const int b = blockIdx.z;
+  int skip = 0;
+  if (PACK) {
+    // block-uniform early-out: every query row of this block is a prefix
+    // row the leader already produced
+    skip = pk_skip[b];
+    if (qb * (NT / 2) + (NT / 2) <= skip) return;
+  }
   const int kvh = h / (H / Hk);
   const int D = 128;
 
@@ -376,6 +389,22 @@ static __device__ __forceinline__ void attn4_body(
     return;
   }
   if (!live) return;
+  if (PACK) {
+    // dead waves of a straddling block took part in every barrier above;
+    // only their store is dropped.  The column bound keeps a bad plan from
+    // writing outside O^T.
+    const long long col = (long long)pk_base[b] + q_lane;
+    if (q_lane < skip || col < 0 || col >= Tp) return;
+    ushort* OTp = OT + (long long)h * D * Tp + col;
+#pragma unroll
+    for (int db = 0; db < 4; ++db)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        OTp[(long long)d * Tp] = f2bf(o_acc[db][r] * inv_l);
+      }
+    return;
+  }
 #pragma unroll
   for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -1150,6 +1179,19 @@ attn_fwd_v4_15_kernel(const ushort* __restrict__ Q,
                       float scale) {
   // reg-stage double-buffer + defer + diet + sm-split
   attn4_body<2, 1, 1, 1>(Q, K, VT, OT, B, H, Hk, S, scale);
+}
+
+// v4_15 for prefix-packed prefill (see attn4_body's PACK note): same body,
+// skipped prefix blocks and a [H*D, Tp] packed O^T.
+extern "C" __global__ void __launch_bounds__(512)
+attn_fwd_v5_packed_kernel(const ushort* __restrict__ Q,
+                          const ushort* __restrict__ K,
+                          const ushort* __restrict__ VT,
+                          ushort* __restrict__ OT, int B, int H, int Hk,
+                          int S, float scale, const int* __restrict__ skip,
+                          const int* __restrict__ base, int Tp) {
+  attn4_body<2, 1, 1, 1, 512, 0, 1>(Q, K, VT, OT, B, H, Hk, S, scale, skip,
+                                    base, Tp);
 }
 
 extern "C" __global__ void __launch_bounds__(256)

@@ -227,6 +227,33 @@ torch::Tensor swiglu(torch::Tensor gateup) {
   return y;
 }
 
+// swiglu into a buffer of out_rows >= rows rows; the rows past the input's
+// are zero.  Lets the caller run the next GEMM at a row count of its choice
+// without a pad copy of the activation.
+torch::Tensor swiglu_padded(torch::Tensor gateup, int64_t out_rows) {
+  check_bf16(gateup, "gateup");
+  TORCH_CHECK(gateup.dim() == 2, "swiglu_padded: gateup must be [rows, 2*inter]");
+  const int inter2 = gateup.size(1);
+  TORCH_CHECK(inter2 % 16 == 0);
+  const int inter = inter2 / 2;
+  const long long rows = gateup.size(0);
+  TORCH_CHECK(out_rows >= rows, "swiglu_padded: out_rows < rows");
+  auto y = torch::empty({out_rows, (int64_t)inter}, gateup.options());
+  const int nvec_blocks = (inter / 8 + 255) / 256;
+  if (rows > 0) {
+    swiglu_fwd_kernel<<<dim3(nvec_blocks, (unsigned)rows), dim3(256), 0, cur_stream()>>>(
+        bf16_ptr(gateup), bf16_mut(y), rows, inter);
+    HIP_CHECK_KERNEL();
+  }
+  if (out_rows > rows) {
+    TORCH_CHECK(hipMemsetAsync(bf16_mut(y) + rows * inter, 0,
+                               (size_t)(out_rows - rows) * inter * sizeof(ushort),
+                               cur_stream()) == hipSuccess,
+                "swiglu_padded: hipMemsetAsync failed");
+  }
+  return y;
+}
+
 torch::Tensor add_bf16(torch::Tensor a, torch::Tensor b) {
   check_bf16(a, "a");
   check_bf16(b, "b");
@@ -600,6 +627,107 @@ torch::Tensor attn_fwd_v5(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   return ot;
 }
 
+// ---------------- Prefix-packed prefill ----------------
+// skip/base/owner: the per-batch-row layout plan (csrc/README.md, "Packed
+// prefill layout").  They live on the device, so only their form is checked
+// here; the kernels drop any row a bad plan would send out of bounds.
+extern "C" __global__ void rope_scatter_packed_kernel(
+    const ushort*, long long, ushort*, ushort*, const float*, const int*, int,
+    int, int, int, int, const int*, const int*, const int*, long long);
+extern "C" __global__ void transpose_v_packed_kernel(
+    const ushort*, long long, long long, ushort*, int, int, int, int,
+    const int*, const int*, const int*, long long);
+extern "C" __global__ void attn_fwd_v5_packed_kernel(
+    const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int,
+    float, const int*, const int*, int);
+
+static void check_plan(const torch::Tensor& t, int64_t B, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                  t.is_contiguous() && t.dim() == 1 && t.size(0) == B,
+              name, " must be a contiguous int32 GPU tensor of length B");
+}
+
+std::vector<torch::Tensor> rope_scatter_qkv_packed(
+    torch::Tensor qkv, torch::Tensor cos_sin, torch::Tensor positions,
+    int64_t Hq, int64_t Hk, int64_t D, int64_t B, int64_t S,
+    torch::Tensor skip, torch::Tensor base, torch::Tensor owner) {
+  check_bf16(qkv, "qkv");
+  const long long Tp = qkv.size(0);
+  const long long ld = qkv.size(1);
+  TORCH_CHECK(qkv.dim() == 2 && Tp <= B * S && B * S < (1LL << 31) &&
+              cos_sin.size(1) == D && ld >= (Hq + 2 * Hk) * D);
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == torch::kFloat32 &&
+              cos_sin.is_contiguous());
+  TORCH_CHECK(positions.is_cuda() && positions.scalar_type() == torch::kInt32 &&
+              positions.is_contiguous() && positions.numel() == Tp,
+              "positions must be int32 [Tp] (one per packed row)");
+  TORCH_CHECK((D / 2) % 8 == 0 && ld % 8 == 0, "rope_scatter needs D/2 % 8 == 0");
+  check_plan(skip, B, "skip");
+  check_plan(base, B, "base");
+  check_plan(owner, B, "owner");
+  auto qo = torch::empty({B, Hq, S, D}, qkv.options());
+  auto ko = torch::empty({B, Hk, S, D}, qkv.options());
+  const int heads_per_blk = (int)(256 / (D / 16));
+  rope_scatter_packed_kernel<<<dim3((unsigned)(B * S), (unsigned)((Hq + Hk + heads_per_blk - 1) / heads_per_blk)),
+                               dim3(256), 0, cur_stream()>>>(
+      bf16_ptr(qkv), ld, bf16_mut(qo), bf16_mut(ko),
+      cos_sin.data_ptr<float>(), positions.data_ptr<int>(), (int)Hq, (int)Hk,
+      (int)D, (int)S, (int)B, skip.data_ptr<int>(), base.data_ptr<int>(),
+      owner.data_ptr<int>(), Tp);
+  HIP_CHECK_KERNEL();
+  return {qo, ko};
+}
+
+torch::Tensor vt_from_qkv_packed(torch::Tensor qkv, int64_t Hq, int64_t Hk,
+                                 int64_t D, int64_t B, int64_t S,
+                                 torch::Tensor skip, torch::Tensor base,
+                                 torch::Tensor owner) {
+  check_bf16(qkv, "qkv");
+  const long long Tp = qkv.size(0);
+  const long long ld = qkv.size(1);
+  TORCH_CHECK(qkv.dim() == 2 && Tp <= B * S && ld >= (Hq + 2 * Hk) * D);
+  TORCH_CHECK(ld % 8 == 0 && D % 8 == 0, "vt_from_qkv: row length and D must be multiples of 8");
+  check_plan(skip, B, "skip");
+  check_plan(base, B, "base");
+  check_plan(owner, B, "owner");
+  auto vt = torch::empty({B, Hk, D, S}, qkv.options());
+  const long long v_off = (Hq + Hk) * D;
+  transpose_v_packed_kernel<<<dim3((unsigned)((S + 31) / 32), (unsigned)((D + 63) / 64),
+                                  (unsigned)(B * Hk)),
+                              dim3(256), 0, cur_stream()>>>(
+      bf16_ptr(qkv), ld, v_off, bf16_mut(vt), (int)B, (int)S, (int)Hk, (int)D,
+      skip.data_ptr<int>(), base.data_ptr<int>(), owner.data_ptr<int>(), Tp);
+  HIP_CHECK_KERNEL();
+  return vt;
+}
+
+// attn_fwd_v5 on prefix-packed rows: returns ONE O^T [H*D, Tp]; query rows
+// below skip[b] are the leader's and are not computed
+torch::Tensor attn_fwd_v5_packed(torch::Tensor q, torch::Tensor k,
+                                 torch::Tensor vt, double scale,
+                                 torch::Tensor skip, torch::Tensor base,
+                                 int64_t Tp) {
+  check_bf16(q, "q");
+  check_bf16(k, "k");
+  check_bf16(vt, "vt");
+  TORCH_CHECK(q.dim() == 4, "attn_fwd_v5_packed: q must be [B,H,S,D]");
+  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+  const int Hk = k.size(1);
+  TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
+  TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
+  check_attn_kv(k, vt, B, S, D, "attn_fwd_v5_packed");
+  TORCH_CHECK(Tp > 0 && Tp <= (int64_t)B * S && (int64_t)B * S < (1LL << 31),
+              "attn_fwd_v5_packed: Tp must be in (0, B*S]");
+  check_plan(skip, B, "skip");
+  check_plan(base, B, "base");
+  auto ot = torch::empty({(int64_t)H * D, Tp}, q.options());
+  attn_fwd_v5_packed_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
+      bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S,
+      (float)scale, skip.data_ptr<int>(), base.data_ptr<int>(), (int)Tp);
+  HIP_CHECK_KERNEL();
+  return ot;
+}
+
 // ---------------- Paged decode attention ----------------
 torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor kcache,
                                 torch::Tensor vcache, torch::Tensor block_table,
@@ -662,6 +790,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_append", &rope_kv_append, "decode: slice+RoPE+KV-append in one kernel");
   m.def("gemv_norm_bt", &gemv_norm_bt, "decode: fused add+RMSNorm+GEMV");
   m.def("swiglu", &swiglu, "silu(gate)*up from fused gateup");
+  m.def("swiglu_padded", &swiglu_padded,
+        "swiglu into [out_rows, inter]; rows past the input's are zero");
   m.def("add_bf16", &add_bf16, "a + b (bf16)");
   m.def("gemm_bt", &gemm_bt, "C = A @ B^T (bf16 MFMA)");
   m.def("gemm_bt_8ph", [](torch::Tensor a, torch::Tensor b) {
@@ -864,6 +994,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_v3", &attn_fwd_v3, "v2 with 8-wave shared K/V tiles; O^T out");
   m.def("attn_fwd_v4", &attn_fwd_v4, "v4 lever-matrix probe (variant arg)");
   m.def("attn_fwd_v5", &attn_fwd_v5, "production attention (v4 winner); O^T out");
+  m.def("rope_scatter_qkv_packed", &rope_scatter_qkv_packed,
+        "rope_scatter_qkv reading prefix-packed qkv rows");
+  m.def("vt_from_qkv_packed", &vt_from_qkv_packed,
+        "vt_from_qkv reading prefix-packed qkv rows");
+  m.def("attn_fwd_v5_packed", &attn_fwd_v5_packed,
+        "attn_fwd_v5 skipping shared-prefix query rows; packed O^T [H*D, Tp] out");
   m.def("paged_decode_attn", &paged_decode_attn, "paged decode attention");
   m.def("argmax_rows", &argmax_rows, "row argmax over bf16 logits");
   m.def("target_logprob", &target_logprob, "fused log_softmax gather");

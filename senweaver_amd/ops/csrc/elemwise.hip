@@ -107,12 +107,33 @@ rope_fwd_kernel(ushort* __restrict__ q, ushort* __restrict__ k,
 // plus two transpose copies (one full q/k read+write each) with one pass.
 // Grid: (T, ceil((Hq+Hk)/heads_per_blk)), 256 threads covering several heads.
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256)
-rope_scatter_kernel(const ushort* __restrict__ qkv, long long ld,
-                    ushort* __restrict__ q_out, ushort* __restrict__ k_out,
-                    const float* __restrict__ cos_sin,
-                    const int* __restrict__ positions, int Hq, int Hk, int D,
-                    int S) {
+//
+// Prefix-packed prefill (PACKED): qkv holds Tp <= B*S packed rows.  A group
+// of batch rows sharing a token prefix stores the prefix once, in its first
+// row (the leader, owner[b] == b); a member stores only s >= skip[b].  The
+// packed row of (b, s) is
+//     s <  skip[b] :  base[owner[b]] + s
+//     s >= skip[b] :  base[b] + s
+// The grid still runs over the B*S OUTPUT rows, so the prefix is broadcast
+// to every member and q_out/k_out are fully written.
+// ---------------------------------------------------------------------------
+static __device__ __forceinline__ long long packed_src_row(
+    int b, int s, int B, const int* __restrict__ skip,
+    const int* __restrict__ base, const int* __restrict__ owner) {
+  int src_b = b;
+  if (s < skip[b]) src_b = owner[b];
+  if ((unsigned)src_b >= (unsigned)B) return -1;  // bad plan: caller drops it
+  return (long long)base[src_b] + s;
+}
+
+template <bool PACKED>
+static __device__ __forceinline__ void rope_scatter_body(
+    const ushort* __restrict__ qkv, long long ld,
+    ushort* __restrict__ q_out, ushort* __restrict__ k_out,
+    const float* __restrict__ cos_sin,
+    const int* __restrict__ positions, int Hq, int Hk, int D,
+    int S, int B, const int* __restrict__ skip, const int* __restrict__ base,
+    const int* __restrict__ owner, long long Tp) {
   // reads q/k heads straight out of the fused qkv GEMM output (row stride
   // ld = q_size + 2*kv_size) — no separate contiguous slice copies.
   // 256-thread blocks cover (256 / (D/2)) heads each: adjacent heads read
@@ -126,16 +147,22 @@ rope_scatter_kernel(const ushort* __restrict__ qkv, long long ld,
   if (h >= Hq + Hk) return;
   const int b = t / S;
   const int s = t % S;
+  // source row in qkv (and in positions, which is per qkv row)
+  long long tr = t;
+  if (PACKED) {
+    tr = packed_src_row(b, s, B, skip, base, owner);
+    if (tr < 0 || tr >= Tp) return;
+  }
   const ushort* src;
   ushort* dst;
   if (h < Hq) {
-    src = qkv + (long long)t * ld + (long long)h * D;
+    src = qkv + tr * ld + (long long)h * D;
     dst = q_out + (((long long)b * Hq + h) * S + s) * D;
   } else {
-    src = qkv + (long long)t * ld + (long long)Hq * D + (long long)(h - Hq) * D;
+    src = qkv + tr * ld + (long long)Hq * D + (long long)(h - Hq) * D;
     dst = k_out + (((long long)b * Hk + (h - Hq)) * S + s) * D;
   }
-  const float* cs = cos_sin + (long long)positions[t] * D;
+  const float* cs = cos_sin + (long long)positions[tr] * D;
   const int d0 = (threadIdx.x % lanes_per_head) * 8;
   // 16-B vector loads/stores (scalar bf16 stores ran this at ~2 TB/s)
   bf16x8 x1 = *reinterpret_cast<const bf16x8*>(src + d0);
@@ -152,6 +179,29 @@ rope_scatter_kernel(const ushort* __restrict__ qkv, long long ld,
   }
   *reinterpret_cast<bf16x8*>(dst + d0) = o1;
   *reinterpret_cast<bf16x8*>(dst + d0 + half) = o2;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+rope_scatter_kernel(const ushort* __restrict__ qkv, long long ld,
+                    ushort* __restrict__ q_out, ushort* __restrict__ k_out,
+                    const float* __restrict__ cos_sin,
+                    const int* __restrict__ positions, int Hq, int Hk, int D,
+                    int S) {
+  rope_scatter_body<false>(qkv, ld, q_out, k_out, cos_sin, positions, Hq, Hk,
+                           D, S, 0, nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+rope_scatter_packed_kernel(const ushort* __restrict__ qkv, long long ld,
+                           ushort* __restrict__ q_out,
+                           ushort* __restrict__ k_out,
+                           const float* __restrict__ cos_sin,
+                           const int* __restrict__ positions, int Hq, int Hk,
+                           int D, int S, int B, const int* __restrict__ skip,
+                           const int* __restrict__ base,
+                           const int* __restrict__ owner, long long Tp) {
+  rope_scatter_body<true>(qkv, ld, q_out, k_out, cos_sin, positions, Hq, Hk,
+                          D, S, B, skip, base, owner, Tp);
 }
 
 // ---------------------------------------------------------------------------
@@ -203,9 +253,14 @@ add_bf16_kernel(const ushort* __restrict__ a, const ushort* __restrict__ b,
 // along s — replaces a strided torch permute().contiguous() that ran ~4x off
 // bandwidth.  Guards handle S not a multiple of 32.
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256)
-transpose_v_kernel(const ushort* __restrict__ qkv, long long ld, long long v_off,
-                   ushort* __restrict__ vt, int B, int S, int Hk, int D) {
+// PACKED: row (b, s) comes from the packed qkv row given by packed_src_row
+// (rope_scatter above), so every member's V^T carries the shared prefix.
+template <bool PACKED>
+static __device__ __forceinline__ void transpose_v_body(
+    const ushort* __restrict__ qkv, long long ld, long long v_off,
+    ushort* __restrict__ vt, int B, int S, int Hk, int D,
+    const int* __restrict__ skip, const int* __restrict__ base,
+    const int* __restrict__ owner, long long Tp) {
   // 16-B vector loads AND stores (the elementwise version's 2-B scalar
   // stores ran ~0.9 TB/s).  32 s-rows x 64 d-cols per block keeps all 256
   // threads busy in both phases; row pad of 8 (72-ushort stride) preserves
@@ -223,12 +278,21 @@ transpose_v_kernel(const ushort* __restrict__ qkv, long long ld, long long v_off
     const int s = s0 + row;
     const int d = d0 + sub * 8;
     if (s < S && d < D) {
-      if (d + 7 < D) {
-        *reinterpret_cast<bf16x8*>(&tile[row][sub * 8]) =
-            *reinterpret_cast<const bf16x8*>(src + (long long)s * ld + d);
-      } else {
-        for (int j = 0; j < 8 && d + j < D; ++j)
-          tile[row][sub * 8 + j] = src[(long long)s * ld + d + j];
+      const ushort* rp = src + (long long)s * ld + d;
+      bool ok = true;
+      if (PACKED) {
+        const long long tr = packed_src_row(b, s, B, skip, base, owner);
+        ok = tr >= 0 && tr < Tp;
+        rp = qkv + tr * ld + v_off + (long long)hk * D + d;
+      }
+      if (ok) {
+        if (d + 7 < D) {
+          *reinterpret_cast<bf16x8*>(&tile[row][sub * 8]) =
+              *reinterpret_cast<const bf16x8*>(rp);
+        } else {
+          for (int j = 0; j < 8 && d + j < D; ++j)
+            tile[row][sub * 8 + j] = rp[j];
+        }
       }
     }
   }
@@ -251,6 +315,23 @@ transpose_v_kernel(const ushort* __restrict__ qkv, long long ld, long long v_off
       }
     }
   }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+transpose_v_kernel(const ushort* __restrict__ qkv, long long ld, long long v_off,
+                   ushort* __restrict__ vt, int B, int S, int Hk, int D) {
+  transpose_v_body<false>(qkv, ld, v_off, vt, B, S, Hk, D, nullptr, nullptr,
+                          nullptr, 0);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+transpose_v_packed_kernel(const ushort* __restrict__ qkv, long long ld,
+                          long long v_off, ushort* __restrict__ vt, int B,
+                          int S, int Hk, int D, const int* __restrict__ skip,
+                          const int* __restrict__ base,
+                          const int* __restrict__ owner, long long Tp) {
+  transpose_v_body<true>(qkv, ld, v_off, vt, B, S, Hk, D, skip, base, owner,
+                         Tp);
 }
 
 // ---------------------------------------------------------------------------

@@ -78,6 +78,30 @@ def attn_fwd_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float
     return torch.einsum("bhst,bhtd->bhsd", p, vf).to(q.dtype)
 
 
+def packed_src_rows_ref(B: int, S: int, skip: torch.Tensor, base: torch.Tensor,
+                        owner: torch.Tensor) -> torch.Tensor:
+    """Prefix-packed prefill: packed row of every (b, s), as int64 [B, S].
+
+    s >= skip[b] lives at base[b] + s; the shared prefix s < skip[b] lives
+    once, in the leader's rows, at base[owner[b]] + s."""
+    s = torch.arange(S, device=skip.device).unsqueeze(0)
+    skip, base, owner = skip.long(), base.long(), owner.long()
+    own = s >= skip.unsqueeze(1)
+    return torch.where(own, base.unsqueeze(1) + s, base[owner].unsqueeze(1) + s)
+
+
+def pack_ot_ref(ot: torch.Tensor, skip: torch.Tensor, base: torch.Tensor,
+                Tp: int) -> torch.Tensor:
+    """O^T [B,H,D,S] -> packed O^T [H*D, Tp]: column base[b] + s holds row
+    (b, s) for s >= skip[b] (prefix columns come from the leader alone)."""
+    B, H, D, S = ot.shape
+    out = torch.zeros(H * D, Tp, dtype=ot.dtype, device=ot.device)
+    for b in range(B):
+        sk, bs = int(skip[b]), int(base[b])
+        out[:, bs + sk: bs + S] = ot[b, :, :, sk:].reshape(H * D, S - sk)
+    return out
+
+
 def paged_decode_attn_ref(q, kcache, vcache, block_table, ctx_lens, scale):
     """q: [B,H,D]; caches [P, 16, Hk, D]; fp32 math."""
     B, H, D = q.shape
