@@ -47,6 +47,81 @@ def bench_gemm():
         print(f"GEMM {M}x{N}x{K}: ours {tf:7.1f} TF/s   hipblaslt {tf2:7.1f} TF/s")
 
 
+def event_us(fn, n_rot, warmup=3, iters=10):
+    """Device time per call in us; fn(i) runs on rotation slot i % n_rot."""
+    for i in range(warmup):
+        fn(i % n_rot)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for i in range(iters):
+        fn((warmup + i) % n_rot)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def gemm_lt_table(M, N, K, transposed=False, verbose=True, label=""):
+    """The tuner's candidate table for one GEMM, next to torch.matmul on the
+    same inputs.  B rotates over enough distinct buffers to exceed the
+    256 MB Infinity Cache, so every timing reads its weights from HBM."""
+    dev = torch.device("cuda:0")
+    ext = ops.hip_ext()
+    n_rot = max(1, min(32, -(-(320 << 20) // (N * K * 2))))
+    bs = [torch.randn(N, K, dtype=torch.bfloat16, device=dev) for _ in range(n_rot)]
+    if transposed:
+        a = torch.randn(K, M, dtype=torch.bfloat16, device=dev).t()
+    else:
+        a = torch.randn(M, K, dtype=torch.bfloat16, device=dev)
+    t_torch = [event_us(lambda i: torch.matmul(a, bs[i].t()), n_rot) for _ in range(3)]
+    r = ext.gemm_lt_tune(a, bs[0], 0, bs, True)
+    t_lt = [event_us(lambda i: ext.gemm_lt(a, bs[i]), n_rot) for _ in range(3)]
+    cands = r["candidates"]
+    timed = [c for c in cands if c["status"] == "timed"]
+    fl = 2.0 * M * N * K
+    lay = "A^T view" if transposed else "row-major"
+    print(f"{label or 'gemm'} M={M} N={N} K={K} {lay}: status {r['status']}, "
+          f"{len(cands)} candidates ({len(timed)} timed in full, "
+          f"{sum(c['status'] == 'not reproducible' for c in cands)} not reproducible), "
+          f"tuning took {r['tune_ms']:.0f} ms, rotation {n_rot} x {N * K * 2 >> 20} MB")
+    print(f"  torch.matmul        {min(t_torch):8.1f} us  (3 runs: "
+          f"{' '.join(f'{t:.1f}' for t in t_torch)})  {fl / min(t_torch) / 1e9:.3f} PF/s")
+    print(f"  first choice        {r['first_us']:8.1f} us  [{cands[0]['index']}] {cands[0]['name'][:90]}")
+    ch = cands[r["chosen"]]
+    print(f"  chosen (cand {r['chosen']:3d})   {r['best_us']:8.1f} us  [{ch['index']}] {ch['name'][:90]}"
+          f"  {fl / r['best_us'] / 1e9:.3f} PF/s")
+    print(f"  gemm_lt as routed   {min(t_lt):8.1f} us  (3 runs: {' '.join(f'{t:.1f}' for t in t_lt)})")
+    if verbose:
+        for c in cands:
+            us = f"{c['us']:8.1f}" if "us" in c else "        "
+            fr = f"{c['first_run_us']:8.1f}" if "first_run_us" in c else "        "
+            print(f"    cand {c['cand']:3d} idx {c['index']:6d} first {fr} avg {us} us  {c['status']}")
+    return min(t_torch), r["first_us"], r["best_us"]
+
+
+def bench_gemm_lt(argv):
+    """kernel_bench.py gemm_lt M N K [t]   one GEMM's candidate table
+    kernel_bench.py gemm_lt bench       the headline bench's GEMM shapes"""
+    if argv and argv[0] != "bench":
+        M, N, K = (int(v) for v in argv[:3])
+        gemm_lt_table(M, N, K, transposed=len(argv) > 3 and argv[3] == "t")
+        return
+    Tp, BS = 6848, 8192   # llama-3-8b, mb4, seq 2048, 500 shared tokens, G=64
+    rows = []
+    for label, M, N, K, t in (("qkv", Tp, 6144, 4096, False),
+                              ("gate|up", Tp, 28672, 4096, False),
+                              ("o_proj", Tp, 4096, 4096, True),
+                              ("o_proj", Tp, 4096, 4096, False),
+                              ("down", Tp, 4096, 14336, False),
+                              ("down", BS, 4096, 14336, False),
+                              ("lm_head", 1600, 128256, 4096, False)):
+        rows.append((label, M, t) + gemm_lt_table(M, N, K, t, verbose=False, label=label))
+        torch.cuda.empty_cache()
+    print("summary (us): GEMM, M, layout, torch.matmul, first choice, best")
+    for label, M, t, tt, tf, tb in rows:
+        print(f"  {label:8s} {M:5d} {'A^T' if t else 'row'}  {tt:8.1f} {tf:8.1f} {tb:8.1f}")
+
+
 def bench_gemm8():
     """A/B: 8-phase pipelined kernel vs the old 256-tile vs hipBLASLt."""
     dev = torch.device("cuda:0")
@@ -160,6 +235,8 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("all", "gemm"):
         bench_gemm()
+    if which == "gemm_lt":
+        bench_gemm_lt(sys.argv[2:])
     if which == "gemm8":
         bench_gemm8()
     if which in ("all", "fp8"):

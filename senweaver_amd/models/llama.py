@@ -155,6 +155,12 @@ class LlamaModel:
             self.lm_head_q, self.lm_head_s = qfn(self.lm_head)
         self.cos_sin = ops.rope_tables(c.max_position, c.head_dim, c.rope_theta).to(self.device)
         self.scale = 1.0 / math.sqrt(c.head_dim)
+        if self.quant == "bf16" and self.device.type == "cuda":
+            # the GEMM tuner times a projection on the weights of ALL layers
+            # in turn (cold from HBM, as in a forward), not on one hot buffer
+            self._gemm_rotations = [
+                ops.register_gemm_rotation([L[name] for L in self.layers])
+                for name in ("qkv", "o", "gateup", "down") if name in self.layers[0]]
 
     def _linear(self, x: torch.Tensor, L: dict, name: str) -> torch.Tensor:
         """Projection through bf16 MFMA or the fp8 MFMA path."""
@@ -217,8 +223,7 @@ class LlamaModel:
                 if self.quant == "bf16":
                     # o_proj directly off the O^T view: hipBLASLt takes the
                     # transposed A natively — no [T, qsize] copy materialized
-                    o = torch.matmul(ot.reshape(B, self.local_q_size, S).transpose(1, 2),
-                                     L["o"].t()).reshape(T, -1)
+                    o = ops.gemm_bt_heads_t(ot.reshape(B, self.local_q_size, S), L["o"])
                     self.tp.all_reduce_(o)
                     h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
                     hidden = self._ffn(h, L)
@@ -242,7 +247,7 @@ class LlamaModel:
     # on Tp rows instead of B*S.  Only rope_scatter, the V^T transpose and
     # the attention epilogue know the mapping: Q/K/V^T are expanded to the
     # ordinary [B, H, S, D] layouts (prefix broadcast to every member) and
-    # attention writes straight into one packed O^T [Hq*D, Tp].
+    # attention writes straight into one packed row-major O [Tp, Hq*D].
     # ------------------------------------------------------------------
     def plan_tensors(self, plan):
         """Device copies of a plan (skip, base, owner int32 [B]; positions
@@ -293,25 +298,62 @@ class LlamaModel:
             vt = ops.vt_from_qkv_packed(qkv, self.local_heads,
                                         self.local_kv_heads, c.head_dim, B, S,
                                         skip, base, owner)
-            ot = ops.attn_fwd_t_packed(qb, kb, vt, self.scale, skip, base, Tp,
+            # packed attention writes O row-major [Tp, Hq*D]: o_proj is a
+            # plain projection (reading A as a transposed view of O^T cost
+            # the GEMM 16%, profiles/gemm_lt_tuning.txt)
+            attn = ops.attn_fwd_packed(qb, kb, vt, self.scale, skip, base, Tp,
                                        flat_idx)
-            if self.quant == "bf16":
-                # one o_proj GEMM off the transposed view (hipBLASLt takes
-                # the transposed A natively)
-                o = torch.matmul(ot.t(), L["o"].t())
+            if self.quant == "bf16" and not attn.is_cuda:
+                # CPU: the bf16 matmul the unpacked path's o_proj uses, so
+                # packed and unpacked stay bit-equal there
+                o = torch.matmul(attn, L["o"].t())
             else:
-                o = self._linear(ot.t().contiguous(), L, "o")
+                o = self._linear(attn, L, "o")
             self.tp.all_reduce_(o)
             h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-            # The down projection stays at the unpacked row count.  Its
-            # N = hidden is only 16 tile columns wide, so B*S rows are a whole
-            # number of waves over the CUs while Tp rows are not, and the
-            # library's stream-K kernel then loses more than the rows save:
-            # measured at Llama-3-8B, 605 us at M=8192 against 901 (M=6848)
-            # and 652 (M=7040) — profiles/prefix_packed_breakdown.txt.  It
-            # also keeps every row's sum order what the unpacked path has.
-            hidden = self._ffn(h, L, down_rows=B * S)
+            hidden = self._ffn(h, L, down_rows=self._down_rows(h, L, B * S))
         return ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
+
+    def _down_rows(self, h: torch.Tensor, L: dict, full_rows: int) -> Optional[int]:
+        """Row count for the packed path's down projection: Tp, or the
+        unpacked B*S with zero rows appended.  N = hidden is only 16 tile
+        columns wide, so B*S rows are a whole number of waves over the CUs
+        while Tp rows are not, and the solution the library's heuristic
+        picks at Tp loses more than the rows save (605 us at M=8192 against
+        901 at M=6848 for Llama-3-8B, profiles/prefix_packed_breakdown.txt).
+        With the tuner on, both row counts are timed with their best
+        solution and the pad is kept only where it still wins clearly with
+        its zero fill counted (profiles/gemm_lt_tuning.txt); the choice is
+        cached per (Tp, B*S).  Without it the pad stays, as measured."""
+        Tp = h.shape[0]
+        if self.quant != "bf16" or "down" not in L or full_rows <= Tp:
+            return None
+        cache = self.__dict__.setdefault("_down_rows_cache", {})
+        hit = cache.get((Tp, full_rows), 0)
+        if hit == 0:
+            hit = full_rows
+            if h.is_cuda:
+                w = L["down"]
+                # random data: an all-zero operand draws less power and
+                # clocks higher, which would flatter both timings
+                act = torch.empty(full_rows, w.shape[1], dtype=h.dtype,
+                                  device=h.device).normal_()
+                act[Tp:].zero_()
+                t_packed = ops.gemm_lt_best_us(act[:Tp], w)
+                t_full = ops.gemm_lt_best_us(act, w)
+                if t_packed is not None and t_full is not None:
+                    fill = ops.hip_ext().gemm_lt_fill_us(
+                        act, (full_rows - Tp) * w.shape[1] * act.element_size())
+                    # the pad has to win by 5%: a choice that timing noise
+                    # can flip would make outputs differ between processes
+                    if t_packed <= 1.05 * (t_full + fill):
+                        hit = None
+                elif torch.cuda.is_current_stream_capturing():
+                    return full_rows  # decided outside a capture
+            if len(cache) >= 64:
+                cache.clear()
+            cache[(Tp, full_rows)] = hit
+        return hit
 
     def _ffn(self, h: torch.Tensor, L: dict,
              down_rows: Optional[int] = None) -> torch.Tensor:

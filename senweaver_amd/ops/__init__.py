@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import Optional
 
 import torch
@@ -210,6 +211,21 @@ def attn_fwd_t_packed(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
     return ot.permute(1, 2, 0, 3).reshape(H * D, B * S).index_select(1, flat_idx)
 
 
+def attn_fwd_packed(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
+                    scale: float, skip, base, Tp: int, flat_idx) -> torch.Tensor:
+    """attn_fwd_t_packed's values as a ROW-MAJOR packed O [Tp, H*D], so that
+    o_proj is an ordinary gemm_bt (the transposed-A GEMM is the library's
+    slowest per FLOP, profiles/gemm_lt_tuning.txt).  Same kernel choice, and
+    bit for bit the transpose of attn_fwd_t_packed's O^T."""
+    B, H, S, D = q.shape
+    if _on_gpu(q) and _ATTN_IMPL != "v2" and ((S + 255) // 256) * B * H >= 512:
+        return hip_ext().attn_fwd_v5_packed_rm(q.contiguous(), k.contiguous(),
+                                               vt.contiguous(), scale, skip,
+                                               base, Tp)
+    ot = attn_fwd_t(q, k, vt, scale)  # [B,H,D,S]
+    return ot.permute(0, 3, 1, 2).reshape(B * S, H * D).index_select(0, flat_idx)
+
+
 def swiglu(gateup: torch.Tensor, out_rows: Optional[int] = None) -> torch.Tensor:
     """silu(gate) * up.  With ``out_rows`` > rows (2-D input) the result has
     out_rows rows, zero past the input's: the next GEMM can run at a row
@@ -225,6 +241,7 @@ def swiglu(gateup: torch.Tensor, out_rows: Optional[int] = None) -> torch.Tensor
 
 
 _GEMM_IMPL = os.environ.get("SENWEAVER_GEMM", "auto")  # auto | hip
+_GEMM_TUNE = os.environ.get("SENWEAVER_GEMM_TUNE", "1") != "0"
 _ATTN_IMPL = os.environ.get("SENWEAVER_ATTN", "auto")  # auto | v2
 
 
@@ -275,6 +292,77 @@ def gemv_mxfp8w(x: torch.Tensor, w_q: torch.Tensor, w_s: torch.Tensor) -> torch.
     return (x.float() @ wf.t()).to(x.dtype)
 
 
+# ---- tuned hipBLASLt dispatch (csrc/gemm_lt.hip) ----
+# torch.matmul runs the solution hipBLASLt's heuristic ranks first; gemm_lt
+# times every candidate once per (M, N, K, A strides) and keeps the winner.
+# _LT_ROUTES remembers, per key, whether the tuned route applies, so a
+# steady-state call costs one dict lookup.
+
+class _Rotation(list):
+    """A list of same-shaped weights (one projection across layers) that the
+    tuner cycles through so B arrives from HBM, as it does in situ."""
+    __slots__ = ("__weakref__",)
+
+
+_ROTATIONS = weakref.WeakValueDictionary()  # weight data_ptr -> _Rotation
+_LT_ROUTES: dict = {}
+
+
+def register_gemm_rotation(weights) -> _Rotation:
+    """Tell the tuner which weights share a shape.  The caller keeps the
+    returned object alive for as long as the weights live."""
+    rot = _Rotation(weights)
+    for w in rot:
+        _ROTATIONS[w.data_ptr()] = rot
+    return rot
+
+
+def _lt_eligible(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if not (a.dim() == 2 and b.dim() == 2 and a.dtype == torch.bfloat16
+            and b.dtype == torch.bfloat16 and b.is_contiguous()):
+        return False
+    M, K = a.shape
+    s0, s1 = a.stride()
+    ok = ((s1 == 1 and s0 >= K and s0 % 8 == 0)
+          or (s0 == 1 and s1 >= M and s1 % 8 == 0))
+    return ok and M > 16 and K % 8 == 0 and b.shape[0] % 8 == 0
+
+
+def gemm_lt_route(a: torch.Tensor, b: torch.Tensor, out_rows: int = 0) -> bool:
+    """True when (a, b) runs on a tuned gemm_lt solution; tunes the key on
+    first sight.  False keeps the caller's torch.matmul route: tuning off,
+    a shape too small to matter, a stream that is capturing a graph, or no
+    usable candidate."""
+    if not _GEMM_TUNE or _GEMM_IMPL == "hip" or not a.is_cuda:
+        return False
+    key = (a.shape, a.stride(), b.shape[0], out_rows)
+    hit = _LT_ROUTES.get(key)
+    if hit is None:
+        if a.data_ptr() % 16 != 0:
+            return False
+        hit = False
+        if _lt_eligible(a, b):
+            rot = _ROTATIONS.get(b.data_ptr())
+            st = hip_ext().gemm_lt_tune(a, b, out_rows, list(rot) if rot else [b],
+                                        False)["status"]
+            if st == "capturing":
+                return False  # not a property of the key: ask again later
+            hit = st in ("tuned", "cached")
+        if len(_LT_ROUTES) >= 1024:
+            _LT_ROUTES.clear()
+        _LT_ROUTES[key] = hit
+    return hit and a.data_ptr() % 16 == 0
+
+
+def gemm_lt_best_us(a: torch.Tensor, b: torch.Tensor, out_rows: int = 0
+                    ) -> Optional[float]:
+    """The tuner's measured time of (a, b) at max(M, out_rows) rows, or None
+    where the key is not on the tuned route."""
+    if not gemm_lt_route(a, b, out_rows):
+        return None
+    return float(hip_ext().gemm_lt_tune(a, b, out_rows, [], False)["best_us"])
+
+
 def gemm_bt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """C[M,N] = A[M,K] @ B[N,K]^T.
 
@@ -283,6 +371,9 @@ def gemm_bt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     skinny); plain prefill GEMMs go to hipBLASLt (1.28-1.58 PF/s at bench
     shapes vs our tiled kernel's 0.88-1.15 — the guide's rule: hand-write the
     fused/special ops, use the vendor library for plain GEMMs it wins).
+    Large bf16 GEMMs run the hipBLASLt solution that timed fastest for their
+    shape (gemm_lt, profiles/gemm_lt_tuning.txt); ``SENWEAVER_GEMM_TUNE=0``
+    leaves the choice to the library's heuristic through torch.matmul.
     ``SENWEAVER_GEMM=hip`` forces the in-repo tiled kernel everywhere.
     """
     if not _on_gpu(a):
@@ -291,8 +382,29 @@ def gemm_bt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     if M <= 16 and b.shape[1] % 512 == 0 and b.shape[0] % 4 == 0:
         return hip_ext().gemm_bt(a.contiguous(), b.contiguous())
     if _GEMM_IMPL != "hip":
+        if _GEMM_TUNE and gemm_lt_route(a, b):
+            return hip_ext().gemm_lt(a, b)
         return a @ b.t()
     return gemm_bt_tiled(a, b)
+
+
+def gemm_bt_heads_t(ot: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """o_proj off attention's native O^T: ot [B, K, S] -> [B*S, N], every
+    batch's A read as the transposed view of its [K, S] slab (no [T, K] copy
+    materialized).  Tuned per-batch GEMMs where the shape is on the tuned
+    route, one batched torch.matmul otherwise."""
+    B, K, S = ot.shape
+    if _on_gpu(ot) and gemm_lt_route(ot[0].t(), b):
+        ext = hip_ext()
+        if B == 1:
+            return ext.gemm_lt(ot[0].t(), b)
+        out = torch.empty(B * S, b.shape[0], dtype=ot.dtype, device=ot.device)
+        for i in range(B):
+            ext.gemm_lt(ot[i].t(), b, 0, out[i * S:(i + 1) * S])
+        return out
+    if B == 1:
+        return torch.matmul(ot[0].t(), b.t())
+    return torch.matmul(ot.transpose(1, 2), b.t()).reshape(B * S, -1)
 
 
 def gemm_bt_tiled(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -19,9 +19,20 @@ SOURCES = [
     os.path.join(CSRC, f)
     for f in ("bindings.hip", "elemwise.hip", "sampling.hip", "gemm.hip",
               "gemm_pipe.hip", "gemm_asm.hip", "attention.hip", "attention_v2.hip",
-              "attention_v4.hip",
+              "attention_v4.hip", "gemm_lt.hip",
               "decode_attention.hip", "moe.hip", "fp8.hip")
 ]
+
+
+def _hipblaslt_ldflags():
+    """Link gemm_lt.hip against the hipBLASLt that libtorch itself loads
+    (torch/lib, SONAME libhipblaslt.so.1): the symbols then resolve to the
+    copy already in the process.  No rpath, so a second copy of the library
+    can never be pulled in."""
+    import torch
+
+    return ["-L" + os.path.join(os.path.dirname(torch.__file__), "lib"),
+            "-lhipblaslt"]
 
 
 def build(verbose: bool = False):
@@ -36,6 +47,7 @@ def build(verbose: bool = False):
         build_directory=BUILD_DIR,
         extra_cflags=["-O3", "-std=c++17"],
         extra_cuda_cflags=["-O3", "-std=c++17"],
+        extra_ldflags=_hipblaslt_ldflags(),
         verbose=verbose,
         with_cuda=True,  # drives hipcc on a ROCm torch build
     )

@@ -89,6 +89,11 @@ static __device__ __forceinline__ float v4_exp2(float x) {
 // recomputed — a block entirely below skip[b] exits before any LDS traffic
 // or barrier, and the epilogue stores row q of batch row b to column
 // base[b] + q of ONE 2-D O^T [H*D, Tp] (row h*D + d) instead of [B,H,D,S].
+// PACK == 2 stores the same values row-major instead, O[Tp, H*D] (packed row
+// base[b] + q, column h*D + d), so that o_proj reads an ordinary row-major
+// A.  (Staging the rows through LDS for fully coalesced 16-byte stores was
+// tried and timed the same, 322.8 against 321.6 us in situ; isolated, both
+// layouts run within 1 us of each other.  The plain stores stay.)
 template <int STAGE, int DEFER, int DIET = 0, int SPLIT = 0,
           int NT = 512, int TEPI = 0, int PACK = 0>
 static __device__ __forceinline__ void attn4_body(
@@ -395,6 +400,24 @@ static __device__ __forceinline__ void attn4_body(
     // writing outside O^T.
     const long long col = (long long)pk_base[b] + q_lane;
     if (q_lane < skip || col < 0 || col >= Tp) return;
+    if (PACK == 2) {
+      // a lane's 64 d values are 16 runs of four consecutive d: 16 stores
+      // of 8 bytes in place of 64 2-byte column stores
+      ushort* Op = OT + col * ((long long)H * D) + h * D + 4 * lhi;
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          // r = 4g .. 4g+3  ->  d = db*32 + 8g + 4*lhi + (0..3)
+          ushort4 v;
+          v.x = f2bf(o_acc[db][g * 4 + 0] * inv_l);
+          v.y = f2bf(o_acc[db][g * 4 + 1] * inv_l);
+          v.z = f2bf(o_acc[db][g * 4 + 2] * inv_l);
+          v.w = f2bf(o_acc[db][g * 4 + 3] * inv_l);
+          *reinterpret_cast<ushort4*>(Op + db * 32 + 8 * g) = v;
+        }
+      return;
+    }
     ushort* OTp = OT + (long long)h * D * Tp + col;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
@@ -1191,6 +1214,18 @@ attn_fwd_v5_packed_kernel(const ushort* __restrict__ Q,
                           int S, float scale, const int* __restrict__ skip,
                           const int* __restrict__ base, int Tp) {
   attn4_body<2, 1, 1, 1, 512, 0, 1>(Q, K, VT, OT, B, H, Hk, S, scale, skip,
+                                    base, Tp);
+}
+
+// The packed kernel with a row-major O [Tp, H*D] (attn4_body's PACK == 2).
+extern "C" __global__ void __launch_bounds__(512)
+attn_fwd_v5_packed_rm_kernel(const ushort* __restrict__ Q,
+                             const ushort* __restrict__ K,
+                             const ushort* __restrict__ VT,
+                             ushort* __restrict__ O, int B, int H, int Hk,
+                             int S, float scale, const int* __restrict__ skip,
+                             const int* __restrict__ base, int Tp) {
+  attn4_body<2, 1, 1, 1, 512, 0, 2>(Q, K, VT, O, B, H, Hk, S, scale, skip,
                                     base, Tp);
 }
 

@@ -641,6 +641,10 @@ extern "C" __global__ void attn_fwd_v5_packed_kernel(
     const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int,
     float, const int*, const int*, int);
 
+extern "C" __global__ void attn_fwd_v5_packed_rm_kernel(
+    const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int,
+    float, const int*, const int*, int);
+
 static void check_plan(const torch::Tensor& t, int64_t B, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
                   t.is_contiguous() && t.dim() == 1 && t.size(0) == B,
@@ -703,10 +707,13 @@ torch::Tensor vt_from_qkv_packed(torch::Tensor qkv, int64_t Hq, int64_t Hk,
 
 // attn_fwd_v5 on prefix-packed rows: returns ONE O^T [H*D, Tp]; query rows
 // below skip[b] are the leader's and are not computed
-torch::Tensor attn_fwd_v5_packed(torch::Tensor q, torch::Tensor k,
-                                 torch::Tensor vt, double scale,
-                                 torch::Tensor skip, torch::Tensor base,
-                                 int64_t Tp) {
+// row_major: O [Tp, H*D] instead of O^T [H*D, Tp]; the same values.  A
+// caller-provided ``out`` lets a test see which rows the kernel leaves alone.
+static torch::Tensor attn_packed_launch(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor vt, double scale,
+                                        torch::Tensor skip, torch::Tensor base,
+                                        int64_t Tp, bool row_major,
+                                        c10::optional<torch::Tensor> out) {
   check_bf16(q, "q");
   check_bf16(k, "k");
   check_bf16(vt, "vt");
@@ -720,12 +727,44 @@ torch::Tensor attn_fwd_v5_packed(torch::Tensor q, torch::Tensor k,
               "attn_fwd_v5_packed: Tp must be in (0, B*S]");
   check_plan(skip, B, "skip");
   check_plan(base, B, "base");
-  auto ot = torch::empty({(int64_t)H * D, Tp}, q.options());
-  attn_fwd_v5_packed_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
-      bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S,
-      (float)scale, skip.data_ptr<int>(), base.data_ptr<int>(), (int)Tp);
+  const std::vector<int64_t> shape = row_major
+      ? std::vector<int64_t>{Tp, (int64_t)H * D}
+      : std::vector<int64_t>{(int64_t)H * D, Tp};
+  torch::Tensor ot;
+  if (out.has_value()) {
+    ot = *out;
+    check_bf16(ot, "out");
+    TORCH_CHECK(ot.sizes().vec() == shape, "attn_fwd_v5_packed: out has the wrong shape");
+    TORCH_CHECK((uintptr_t)ot.data_ptr() % 16 == 0, "attn_fwd_v5_packed: out must be 16-byte aligned");
+  } else {
+    ot = torch::empty(shape, q.options());
+  }
+  const dim3 grid((S + 255) / 256, H, B);
+  if (row_major) {
+    attn_fwd_v5_packed_rm_kernel<<<grid, dim3(512), 0, cur_stream()>>>(
+        bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S,
+        (float)scale, skip.data_ptr<int>(), base.data_ptr<int>(), (int)Tp);
+  } else {
+    attn_fwd_v5_packed_kernel<<<grid, dim3(512), 0, cur_stream()>>>(
+        bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S,
+        (float)scale, skip.data_ptr<int>(), base.data_ptr<int>(), (int)Tp);
+  }
   HIP_CHECK_KERNEL();
   return ot;
+}
+
+torch::Tensor attn_fwd_v5_packed(torch::Tensor q, torch::Tensor k,
+                                 torch::Tensor vt, double scale,
+                                 torch::Tensor skip, torch::Tensor base,
+                                 int64_t Tp) {
+  return attn_packed_launch(q, k, vt, scale, skip, base, Tp, false, c10::nullopt);
+}
+
+torch::Tensor attn_fwd_v5_packed_rm(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor vt, double scale,
+                                    torch::Tensor skip, torch::Tensor base,
+                                    int64_t Tp, c10::optional<torch::Tensor> out) {
+  return attn_packed_launch(q, k, vt, scale, skip, base, Tp, true, out);
 }
 
 // ---------------- Paged decode attention ----------------
@@ -781,7 +820,11 @@ torch::Tensor target_logprob(torch::Tensor logits, torch::Tensor targets) {
   return out;
 }
 
+// gemm_lt.hip: direct hipBLASLt binding with the per-shape tuner
+void register_gemm_lt(pybind11::module_& m);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  register_gemm_lt(m);
   m.def("rmsnorm", &rmsnorm, "RMSNorm fwd (bf16)");
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual += x; y = rmsnorm(residual)");
   m.def("rope_inplace", &rope_inplace, "RoPE in place over q,k");
@@ -998,6 +1041,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "rope_scatter_qkv reading prefix-packed qkv rows");
   m.def("vt_from_qkv_packed", &vt_from_qkv_packed,
         "vt_from_qkv reading prefix-packed qkv rows");
+  m.def("attn_fwd_v5_packed_rm", &attn_fwd_v5_packed_rm,
+        "packed attention, row-major O [Tp, H*D]", pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("vt"), pybind11::arg("scale"), pybind11::arg("skip"),
+        pybind11::arg("base"), pybind11::arg("Tp"), pybind11::arg("out") = pybind11::none());
   m.def("attn_fwd_v5_packed", &attn_fwd_v5_packed,
         "attn_fwd_v5 skipping shared-prefix query rows; packed O^T [H*D, Tp] out");
   m.def("paged_decode_attn", &paged_decode_attn, "paged decode attention");
