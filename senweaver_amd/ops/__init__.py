@@ -498,16 +498,26 @@ def grouped_gemm_bt(a_sorted: torch.Tensor, w: torch.Tensor, seg_starts_cpu,
     device form keeps the whole routed FFN sync-free on the hipBLASLt
     grouped path (torch._grouped_mm takes device offsets directly; the
     per-expert ``int(counts[e])`` host reads were 8 tiny D2H syncs per MoE
-    layer).  With host offsets, ``a_sorted`` may carry >=128 pad rows for
-    the in-repo kernel's tile overread; with device offsets it must be
-    exactly the routed rows.  Returns at least the routed rows; rows past
-    the last segment (if any) are undefined.
+    layer).  With host offsets, ``a_sorted`` holds at least ``starts[-1]``
+    rows and may carry more (pad rows); with device offsets it must be
+    exactly the routed rows.  The in-repo kernel stages whole 128-row tiles:
+    where the last tile would reach past ``a_sorted``, this function pads a
+    copy itself, so callers need no spare rows (a caller that brings them
+    saves the copy).  Returns at least the routed rows; rows past the last
+    segment (if any) are undefined.
     """
     E = w.shape[0]
     dev_offs = (isinstance(seg_starts_cpu, torch.Tensor)
                 and seg_starts_cpu.is_cuda)
     if not dev_offs:
         starts = [int(x) for x in seg_starts_cpu]
+        if len(starts) != E + 1:
+            raise ValueError(f"need {E + 1} segment offsets, got {len(starts)}")
+        if starts[0] < 0 or any(t < s for s, t in zip(starts, starts[1:])):
+            raise ValueError("segment offsets must be non-negative and non-decreasing")
+        if starts[-1] > a_sorted.shape[0]:
+            raise ValueError(f"segments end at row {starts[-1]}, a_sorted has "
+                             f"{a_sorted.shape[0]}")
     if not _on_gpu(a_sorted):
         out = torch.zeros(a_sorted.shape[0], w.shape[1], dtype=a_sorted.dtype)
         for e in range(E):
@@ -532,13 +542,21 @@ def grouped_gemm_bt(a_sorted: torch.Tensor, w: torch.Tensor, seg_starts_cpu,
     if dev_offs:
         # fallback needs host offsets (tile map is host-built) + pad rows
         starts = [0] + seg_starts_cpu.cpu().tolist()
-        a_sorted = torch.nn.functional.pad(a_sorted, (0, 0, 0, 128))
+        if len(starts) != E + 1:
+            raise ValueError(f"need {E} segment ends, got {len(starts) - 1}")
+        if starts[-1] > a_sorted.shape[0]:
+            raise ValueError(f"segments end at row {starts[-1]}, a_sorted has "
+                             f"{a_sorted.shape[0]}")
     tile_expert, tile_m0 = [], []
     for e in range(E):
         s, t = starts[e], starts[e + 1]
         for m0 in range(s, t, 128):
             tile_expert.append(e)
             tile_m0.append(m0)
+    # a tile stages rows [m0, m0 + 128) whatever its segment holds
+    need = max(tile_m0) + 128 if tile_m0 else 0
+    if need > a_sorted.shape[0]:
+        a_sorted = torch.nn.functional.pad(a_sorted, (0, 0, 0, need - a_sorted.shape[0]))
     te = torch.tensor(tile_expert, dtype=torch.int32, device=dev)
     tm = torch.tensor(tile_m0, dtype=torch.int32, device=dev)
     ends = torch.tensor(starts[1:], dtype=torch.int32, device=dev)

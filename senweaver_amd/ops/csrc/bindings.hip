@@ -353,10 +353,23 @@ torch::Tensor grouped_gemm_bt(torch::Tensor A, torch::Tensor W,
   TORCH_CHECK(tile_expert.scalar_type() == torch::kInt32 && tile_expert.is_contiguous());
   TORCH_CHECK(tile_m0.scalar_type() == torch::kInt32 && tile_m0.is_contiguous());
   TORCH_CHECK(seg_ends.scalar_type() == torch::kInt32 && seg_ends.is_contiguous());
+  TORCH_CHECK(A.dim() == 2 && W.dim() == 3, "A must be [T, K], W [E, N, K]");
+  TORCH_CHECK(W.device() == A.device() && tile_expert.device() == A.device() &&
+              tile_m0.device() == A.device() && seg_ends.device() == A.device(),
+              "grouped_gemm_bt operands must be on one device");
+  TORCH_CHECK(tile_expert.dim() == 1 && tile_m0.dim() == 1 && seg_ends.dim() == 1);
+  TORCH_CHECK(seg_ends.size(0) == W.size(0), "seg_ends needs one entry per expert; got ",
+              seg_ends.size(0), " for ", W.size(0), " experts");
+  TORCH_CHECK(tile_m0.size(0) == tile_expert.size(0),
+              "tile_m0 and tile_expert differ in length");
   const int K = A.size(1);
   const int N = W.size(1);
   TORCH_CHECK(W.size(2) == K && N % 128 == 0 && K % 64 == 0);
   const int n_mtiles = tile_expert.size(0);
+  // every tile stages 128 rows of A from its m0, whatever the segment holds
+  TORCH_CHECK(n_mtiles == 0 || A.size(0) >= 128,
+              "grouped_gemm_bt stages 128-row tiles: A needs >= 128 rows (pad); got ",
+              A.size(0));
   const int tiles_n = N / 128;
   auto C = torch::empty({A.size(0), (long)N}, A.options());
   if (n_mtiles > 0) {
@@ -369,13 +382,29 @@ torch::Tensor grouped_gemm_bt(torch::Tensor A, torch::Tensor W,
 }
 
 // ---------------- fp8 path ----------------
+// The tiled quantized GEMMs index A, B and both scale tensors from M, N, K
+// alone: all four on one GPU, contiguous, one scale row per operand row.
+static void check_qgemm_operands(const torch::Tensor& Aq, const torch::Tensor& As,
+                                 const torch::Tensor& Bq, const torch::Tensor& Bs) {
+  TORCH_CHECK(Aq.is_cuda() && As.device() == Aq.device() && Bq.device() == Aq.device() &&
+              Bs.device() == Aq.device(), "quantized GEMM operands must be on one GPU");
+  TORCH_CHECK(Aq.is_contiguous() && As.is_contiguous() && Bq.is_contiguous() &&
+              Bs.is_contiguous(), "quantized GEMM operands must be contiguous");
+  TORCH_CHECK(Aq.dim() == 2 && Bq.dim() == 2, "A_q must be [M, K], B_q [N, K]");
+  TORCH_CHECK(As.dim() >= 1 && As.size(0) == Aq.size(0), "a_s needs one row per row of A_q; got ",
+              As.size(0), " for M=", Aq.size(0));
+  TORCH_CHECK(Bs.dim() >= 1 && Bs.size(0) == Bq.size(0), "b_s needs one row per row of B_q; got ",
+              Bs.size(0), " for N=", Bq.size(0));
+}
+
 std::vector<torch::Tensor> quant_fp8(torch::Tensor x) {
   check_bf16(x, "x");
   const int K = x.size(-1);
-  TORCH_CHECK(K % 8 == 0);
+  TORCH_CHECK(K > 0 && K % 8 == 0);
   const long long rows = x.numel() / K;
   auto q = torch::empty({rows, (long)K}, x.options().dtype(torch::kUInt8));
   auto s = torch::empty({rows}, x.options().dtype(torch::kFloat32));
+  if (rows == 0) return {q, s};
   quant_fp8_rowwise_kernel<<<dim3((unsigned)rows), dim3(256), 0, cur_stream()>>>(
       bf16_ptr(x), q.data_ptr<unsigned char>(), s.data_ptr<float>(), K);
   HIP_CHECK_KERNEL();
@@ -386,6 +415,8 @@ torch::Tensor gemm_bt_fp8(torch::Tensor Aq, torch::Tensor As,
                           torch::Tensor Bq, torch::Tensor Bs) {
   TORCH_CHECK(Aq.scalar_type() == torch::kUInt8 && Bq.scalar_type() == torch::kUInt8);
   TORCH_CHECK(As.scalar_type() == torch::kFloat32 && Bs.scalar_type() == torch::kFloat32);
+  check_qgemm_operands(Aq, As, Bq, Bs);
+  TORCH_CHECK(As.dim() == 1 && Bs.dim() == 1, "fp8 scales are one f32 per row");
   const int M = Aq.size(0), K = Aq.size(1), N = Bq.size(0);
   TORCH_CHECK(Bq.size(1) == K && M % 128 == 0 && N % 128 == 0 && K % 128 == 0,
               "fp8 gemm needs M,N%128, K%128; got ", M, "x", N, "x", K);
@@ -403,10 +434,11 @@ torch::Tensor gemm_bt_fp8(torch::Tensor Aq, torch::Tensor As,
 std::vector<torch::Tensor> quant_mxfp8(torch::Tensor x) {
   check_bf16(x, "x");
   const int K = x.size(-1);
-  TORCH_CHECK(K % 32 == 0, "mxfp8 needs K%32; got ", K);
+  TORCH_CHECK(K > 0 && K % 32 == 0, "mxfp8 needs K%32; got ", K);
   const long long rows = x.numel() / K;
   auto q = torch::empty({rows, (long)K}, x.options().dtype(torch::kUInt8));
   auto s = torch::empty({rows, (long)(K / 32)}, x.options().dtype(torch::kUInt8));
+  if (rows == 0) return {q, s};
   quant_mxfp8_kernel<<<dim3((unsigned)rows), dim3(256), 0, cur_stream()>>>(
       bf16_ptr(x), q.data_ptr<unsigned char>(), s.data_ptr<unsigned char>(), K);
   HIP_CHECK_KERNEL();
@@ -417,6 +449,8 @@ torch::Tensor gemm_bt_mxfp8(torch::Tensor Aq, torch::Tensor As,
                             torch::Tensor Bq, torch::Tensor Bs) {
   TORCH_CHECK(Aq.scalar_type() == torch::kUInt8 && Bq.scalar_type() == torch::kUInt8);
   TORCH_CHECK(As.scalar_type() == torch::kUInt8 && Bs.scalar_type() == torch::kUInt8);
+  check_qgemm_operands(Aq, As, Bq, Bs);
+  TORCH_CHECK(As.dim() == 2 && Bs.dim() == 2, "mx scales are [rows, K/32] e8m0 bytes");
   const int M = Aq.size(0), K = Aq.size(1), N = Bq.size(0);
   TORCH_CHECK(Bq.size(1) == K && M % 128 == 0 && N % 128 == 0 && K % 128 == 0,
               "mxfp8 gemm needs M,N%128, K%128; got ", M, "x", N, "x", K);

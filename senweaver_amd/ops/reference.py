@@ -185,3 +185,10 @@ def gemm_bt_mxfp8_ref(a_q, a_s, b_q, b_s):
         f = q.view(torch.float8_e4m3fn).float().view(rows, K // 32, 32)
         return (f * torch.exp2(s.float() - 127).unsqueeze(-1)).reshape(rows, K)
     return (deq(a_q, a_s) @ deq(b_q, b_s).t()).to(torch.bfloat16)
+
+
+def moe_combine_ref(down, pos, weight):
+    """out[t] = sum_j weight[pos[t, j]] * down[pos[t, j]], fp32 sum, bf16 out.
+    down [P, H] bf16, pos [T, k] int, weight [P] f32."""
+    p = pos.long()
+    return (weight.float()[p].unsqueeze(-1) * down.float()[p]).sum(dim=1).to(down.dtype)

@@ -1,8 +1,10 @@
-"""fp64 oracles, input generators and error bounds for the decode kernels
-and the prefill attention kernels.
+"""fp64 oracles, input generators and error bounds for the decode kernels,
+the prefill attention kernels, the tiled quantized GEMMs (fp8 / mxfp8), the
+grouped GEMM, the quantizers and moe_combine.
 
-Helper module for test_kernel_oracles_cpu.py, test_decode_edges_gpu.py and
-test_prefill_edges_gpu.py (no tests live here).  Every oracle takes the
+Helper module for test_kernel_oracles_cpu.py, test_decode_edges_gpu.py,
+test_prefill_edges_gpu.py and test_quant_gemm_edges_gpu.py (no tests live
+here).  Every oracle takes the
 SAME bf16 / uint8 tensors the kernel gets, upcasts with ``.double()`` and computes in plain torch on the
 CPU, so the only error in an oracle is fp64 rounding (~1e-16 relative).
 
@@ -985,3 +987,568 @@ def check_vt_from_qkv(fn, B, S, Hq, Hk, D, dev, gen, extra_cols=0):
     exp = exp.permute(0, 2, 3, 1).contiguous()
     got = fn(qkv.to(dev), Hq, Hk, D, B, S)
     assert_bits_equal(got, exp, f"vt_from_qkv B={B} S={S} Hq={Hq} Hk={Hk} D={D} ld={ld}")
+
+
+# --------------------------------------------------------------------------
+# Tiled quantized GEMM (e4m3 x e4m3: fp8 row scales / MX e8m0 block scales).
+# The op under test is ``fn(a_q [M,K] u8, a_s, b_q [N,K] u8, b_s) -> C [M,N]
+# bf16`` with a_s / b_s f32 [rows] (kind 'fp8') or u8 [rows, K/32] ('mx').
+# --------------------------------------------------------------------------
+QGEMM_KFACTOR = {"fp8": 32, "mx": 64}   # measured, see check_qgemm_random
+
+
+def assert_bytes_equal(got: torch.Tensor, exp: torch.Tensor, what: str = ""):
+    assert got.dtype == torch.uint8 and exp.dtype == torch.uint8, what
+    assert got.shape == exp.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(exp.shape)}"
+    g = got.detach().cpu()
+    if torch.equal(g, exp):
+        return
+    bad = (g != exp).nonzero()
+    i = tuple(int(v) for v in bad[0])
+    raise AssertionError(f"{what}: {bad.shape[0]} of {g.numel()} bytes differ; first at {i}: "
+                         f"got 0x{int(g[i]):02x} expected 0x{int(exp[i]):02x}")
+
+
+def qgemm_probe_columns(K: int) -> list:
+    """probe_columns(K) plus both sides of every 16 / 32 / 64 / 128 boundary
+    (16-byte LDS chunk, scale block, MFMA step, K-tile) and K - 1."""
+    cols = set(probe_columns(K)) | {0, K - 1}
+    for step in (16, 32, 64, 128):
+        for b in range(step, K, step):
+            cols.update((b - 1, b))
+    return sorted(c for c in cols if 0 <= c < K)
+
+
+def qgemm_onehot_cols(M: int, K: int) -> torch.Tensor:
+    """Row m probes column cols[m % len(cols)]."""
+    cols = qgemm_probe_columns(K)
+    return torch.tensor([cols[m % len(cols)] for m in range(M)])
+
+
+def mx_probe_scales(gen, M: int, N: int, nblk: int):
+    """e8m0 bytes (A [M, nblk], B [N, nblk]) for the one-hot probe.  Within
+    a row every block has another exponent (a random injection of the blocks
+    into R = max(nblk, 8) slots); A's exponents are even, B's odd, so no A
+    row equals any B row in any block.  One A row is lifted by +40 and one B
+    row lowered by 40 (bytes near 167 / 87).  |exponent| <= R + 40 per side;
+    with e4m3 products in 2^-18 .. 2^18 the outputs stay within 2^+-122."""
+    assert nblk <= 32
+    R = max(nblk, 8)
+
+    def perms(rows):
+        return torch.rand(rows, R, generator=gen).argsort(dim=1)[:, :nblk]
+
+    ea = 2 * perms(M) - R
+    eb = 2 * perms(N) - R + 1
+    ea[min(1, M - 1)] += 40
+    eb[min(2, N - 1)] -= 40
+    return (ea + 127).to(torch.uint8), (eb + 127).to(torch.uint8)
+
+
+def make_qgemm_case(kind: str, mode: str, gen, M: int, N: int, K: int):
+    """mode 'onehot' | 'int' | 'random'.  Returns ((a_q, a_s, b_q, b_s),
+    a64 [M,K], b64 [N,K]) with a64 / b64 the dequantized operands."""
+    assert kind in ("fp8", "mx") and K % 32 == 0
+    nblk = K // 32
+
+    def pow2_rows(rows):
+        return torch.exp2(torch.randint(-3, 4, (rows,), generator=gen).float())
+
+    if mode == "onehot":
+        a_q = torch.zeros(M, K, dtype=torch.uint8)
+        a_q[torch.arange(M), qgemm_onehot_cols(M, K)] = _rand_e4m3_bytes(gen, M, 1)[:, 0]
+        b_q = _rand_e4m3_bytes(gen, N, K)
+        if kind == "fp8":
+            a_s, b_s = pow2_rows(M), pow2_rows(N)
+        else:
+            a_s, b_s = mx_probe_scales(gen, M, N, nblk)
+    elif mode == "int":
+        a_q, b_q = _int_e4m3_bytes(gen, M, K), _int_e4m3_bytes(gen, N, K)
+        if kind == "fp8":
+            a_s, b_s = pow2_rows(M), pow2_rows(N)
+        else:   # 2^-2 .. 2^2 per block: every product is a multiple of 2^-4
+            a_s = torch.randint(125, 130, (M, nblk), generator=gen).to(torch.uint8)
+            b_s = torch.randint(125, 130, (N, nblk), generator=gen).to(torch.uint8)
+    elif mode == "random":
+        a_q, b_q = _rand_e4m3_bytes(gen, M, K), _rand_e4m3_bytes(gen, N, K)
+        if kind == "fp8":
+            a_s = ((2.0 ** -4) * (1.0 + torch.rand(M, generator=gen))).float()
+            b_s = ((2.0 ** -4) * (1.0 + torch.rand(N, generator=gen))).float()
+        else:   # random e8m0 over +-6
+            a_s = torch.randint(121, 134, (M, nblk), generator=gen).to(torch.uint8)
+            b_s = torch.randint(121, 134, (N, nblk), generator=gen).to(torch.uint8)
+    else:
+        raise ValueError(mode)
+    deq = dequant_fp8_ref64 if kind == "fp8" else dequant_mx_ref64
+    return (a_q, a_s, b_q, b_s), deq(a_q, a_s), deq(b_q, b_s)
+
+
+def qgemm_int_premise(kind, args, a64, b64) -> float:
+    """Largest sum of |products| in units of the smallest product quantum;
+    below 2^24 every partial sum, in any order, is exact in fp32.  fp8: the
+    accumulator holds the UNSCALED integer sum (scales are applied after);
+    mx: scaled products are multiples of 2^-4."""
+    if kind == "fp8":
+        a, b = e4m3_to_f64(args[0]), e4m3_to_f64(args[2])
+        return float((a.abs() @ b.abs().t()).max())
+    return float((a64.abs() @ b64.abs().t()).max()) * 16
+
+
+def check_qgemm_onehot(fn, kind, M, N, K, dev, gen):
+    """Row m of A_q has one non-zero byte, at a probe column; scales are
+    powers of two (mx: another exponent for every (row, block)).  a * b has
+    at most 8 significant bits, so C[m, n] = a b 2^(..) is a bf16 value and
+    must come out bit for bit, for every m and n.  For kind 'mx' this pins
+    the scale byte <-> K block mapping of both operands."""
+    args, a64, b64 = make_qgemm_case(kind, "onehot", gen, M, N, K)
+    ref = a64 @ b64.t()
+    exp = exact_bf16(ref)
+    assert torch.equal(exp.double(), ref), "generator: expectation is not a bf16 value"
+    got = fn(*_to(dev, args))
+    assert_bits_equal(got, exp, f"{kind} qgemm one-hot M={M} N={N} K={K}")
+
+
+def check_qgemm_int(fn, kind, M, N, K, dev, gen):
+    """Small integers over all of K with power-of-two scales: every partial
+    sum is exact in fp32, so C == bf16_rne(exact sum) bit for bit.  Catches
+    a dropped or doubled K-tile, a wrong swizzle or buffer parity and a hole
+    in the workgroup remap."""
+    args, a64, b64 = make_qgemm_case(kind, "int", gen, M, N, K)
+    assert qgemm_int_premise(kind, args, a64, b64) < 2 ** 24
+    exp = exact_bf16(a64 @ b64.t())
+    got = fn(*_to(dev, args))
+    assert_bits_equal(got, exp, f"{kind} qgemm integer M={M} N={N} K={K}")
+
+
+def check_qgemm_random(fn, kind, M, N, K, dev, gen, kfactor=None):
+    """Random finite bytes, non-power-of-two f32 row scales (fp8) / random
+    e8m0 over +-6 (mx).  Elementwise bound: gemv_bound(ref, |A|.|B|^T, K,
+    kfactor) — bf16 output rounding plus worst-case fp32 summation in any
+    order (e4m3 x e4m3 products are exact) — plus 2 * 2^-24 |ref| for the fp8
+    epilogue's two f32 multiplies.
+
+    kfactor = 1 does not hold on the MI355X: the fp8 MFMAs do not add their
+    32 / 64 products as separately rounded fp32 terms (the error pattern is
+    that of small products losing bits against the largest one of the
+    instruction — random e4m3 bytes span 2^36 in the products; integer and
+    one-hot data stay bit-exact).  Measured against this fp64 reference on every
+    (M, N, K) of tests/test_quant_gemm_edges_gpu.py, three draws each, the
+    worst err / bound at kfactor = 1 was 12.2 for fp8 (at K = 128; 1.3 at
+    K = 640) and 19.3 for mx (at 2560 x 4352 x 128; 13.3 at the shapes the
+    random tests run).  The excess is about 1000 .. 3400 x 2^-24 |A|.|B|^T
+    whatever K is.  QGEMM_KFACTOR is the smallest power of two that leaves a
+    2x margin over those ratios: 32 for fp8, 64 for mx.  The CPU fallbacks
+    (true fp32 sums) stay below 1.0 at kfactor = 1.
+    Returns (and prints) the worst err / bound."""
+    args, a64, b64 = make_qgemm_case(kind, "random", gen, M, N, K)
+    ref = a64 @ b64.t()
+    absdot = a64.abs() @ b64.abs().t()
+    bound = gemv_bound(ref, absdot, K, QGEMM_KFACTOR[kind] if kfactor is None else kfactor)
+    if kind == "fp8":
+        bound = bound + 2 * U_FP32 * ref.abs()
+    got = fn(*_to(dev, args))
+    what = f"{kind} qgemm random M={M} N={N} K={K}"
+    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)}"
+    err = (got.detach().cpu().double() - ref).abs()
+    ratio = float((err / bound).max())
+    # the summation term on its own: error left after a full bf16 half-ulp
+    excess = float(((err - U_BF16_OUT * ref.abs()) / (K * U_FP32 * absdot)).max())
+    print(f"{what}: max err / bound = {ratio:.3f}; "
+          f"max (err - 2^-8|ref|) / (K 2^-24 |A|.|B|) = {excess:.3f}")
+    assert_within(got, ref, bound, what)
+    return ratio
+
+
+# --------------------------------------------------------------------------
+# Grouped GEMM (MoE).  ``fn(a_sorted [T,K] bf16, w [E,N,K] bf16, seg) -> C``
+# with seg a host list of E+1 offsets or a device int32 tensor of E ends.
+# --------------------------------------------------------------------------
+def make_grouped_case(gen, sizes, N, K, mode):
+    """Expert-sorted activations and per-expert weights that differ from
+    every other expert's in EVERY element.  mode 'int': A in [-2, 2],
+    W[e] = ((base + e) mod 9) - 4; 'random': A randn, W[e] = r 2^(e - E/2)
+    with one shared non-zero r.  Returns (a, w, starts, ref64, absdot)."""
+    E, T = len(sizes), sum(sizes)
+    assert 1 <= E <= 9
+    if mode == "int":
+        a = int_x(gen, T, K)
+        base = torch.randint(0, 9, (N, K), generator=gen)
+        w = torch.stack([((base + e) % 9) - 4 for e in range(E)]).to(BF16)
+    elif mode == "random":
+        a = rand_bf16(gen, T, K)
+        r = clamp_v(rand_bf16(gen, N, K))
+        w = torch.stack([(r.float() * 2.0 ** (e - E // 2)).to(BF16) for e in range(E)])
+    else:
+        raise ValueError(mode)
+    for e in range(E):
+        for f in range(e + 1, E):
+            assert bool((w[e] != w[f]).all()), "generator: experts share an element"
+    starts = [0]
+    for s in sizes:
+        starts.append(starts[-1] + s)
+    ref = torch.zeros(T, N, dtype=torch.float64)
+    absdot = torch.zeros(T, N, dtype=torch.float64)
+    for e in range(E):
+        s, t = starts[e], starts[e + 1]
+        ref[s:t] = a[s:t].double() @ w[e].double().t()
+        absdot[s:t] = a[s:t].double().abs() @ w[e].double().abs().t()
+    return a, w, starts, ref, absdot
+
+
+def check_grouped_gemm(fn, sizes, N, K, dev, gen, offsets="host"):
+    """Every row of every segment (so both sides of each segment end): bit
+    for bit on integer data, within the bf16 GEMV bound on random data.
+    ``a_sorted`` is passed with exactly sum(sizes) rows — no spare rows."""
+    T = sum(sizes)
+    for mode in ("int", "random"):
+        a, w, starts, ref, absdot = make_grouped_case(gen, sizes, N, K, mode)
+        if offsets == "host":
+            seg = list(starts)
+        else:
+            seg = torch.tensor(starts[1:], dtype=torch.int32).to(dev)
+        got = fn(a.to(dev), w.to(dev), seg)
+        what = f"grouped gemm {mode} sizes={sizes} N={N} K={K} offsets={offsets}"
+        assert got.dim() == 2 and got.shape[0] >= T and got.shape[1] == N, \
+            f"{what}: shape {tuple(got.shape)}"
+        got = got[:T]
+        if mode == "int":
+            assert float(absdot.max()) < 2 ** 24
+            assert_bits_equal(got.contiguous(), exact_bf16(ref), what)
+        else:
+            assert_within(got, ref, gemv_bound(ref, absdot, K), what)
+
+
+# --------------------------------------------------------------------------
+# Quantizers
+# --------------------------------------------------------------------------
+E4M3_MAX = 448.0
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e in fp64 for integer e (exact)."""
+    return torch.pow(torch.full((), 2.0, dtype=torch.float64), e.double())
+
+
+def _e4m3_quantum(a: torch.Tensor) -> torch.Tensor:
+    """Spacing of e4m3 values at magnitude a (fp64, a >= 0): 2^(e-3) with
+    e = max(floor(log2 a), -6); 2^-9 in the subnormal range and at 0."""
+    _, ex = torch.frexp(a)
+    e = torch.where(a > 0, ex.long() - 1, torch.full_like(ex.long(), -6)).clamp(min=-6)
+    return _pow2(e - 3)
+
+
+def _e4m3_encode(val: torch.Tensor, neg: torch.Tensor) -> torch.Tensor:
+    """Bytes of non-negative fp64 values that ARE e4m3 values, sign bit from
+    ``neg``."""
+    b = val.float().to(torch.float8_e4m3fn).view(torch.uint8)
+    assert torch.equal(e4m3_to_f64(b), val), "not an e4m3 value"
+    return b | (neg.to(torch.uint8) << 7)
+
+
+def e4m3_rne_bytes(v64: torch.Tensor) -> torch.Tensor:
+    """Round-to-nearest-even of fp64 values to e4m3fn bytes, saturating at
+    448; the sign bit is kept on a zero result.  Written out (not torch's
+    conversion) so the expectation has one rounding, from the exact value."""
+    a = v64.abs().clamp(max=E4M3_MAX)
+    qn = _e4m3_quantum(a)
+    return _e4m3_encode(torch.round(a / qn) * qn, torch.signbit(v64))   # round: half to even
+
+
+def e4m3_neighbours(a: torch.Tensor):
+    """(lo, hi): the e4m3 magnitudes around a >= 0; lo == a when a is one."""
+    qn = _e4m3_quantum(a)
+    lo = torch.floor(a / qn) * qn
+    return lo, lo + qn
+
+
+def all_e4m3_magnitudes() -> torch.Tensor:
+    """The 127 finite e4m3fn magnitudes, ascending (0 .. 448)."""
+    return e4m3_to_f64(torch.arange(0, 0x7f, dtype=torch.uint8))
+
+
+def _bf16_step(v: float, up: bool) -> float:
+    """The bf16 value one ulp above / below a positive bf16 value."""
+    t = torch.tensor([v], dtype=BF16)
+    assert float(t) == v and v > 0
+    return float((t.view(torch.int16) + (1 if up else -1)).view(BF16))
+
+
+def _fill(gen, amax: float, n: int, frac: float = 0.5) -> torch.Tensor:
+    """n bf16 values of magnitude <= frac * amax."""
+    u = torch.rand(n, generator=gen, dtype=torch.float64) * 2 - 1
+    return (u * frac * amax).to(BF16)
+
+
+def _midpoint_block() -> torch.Tensor:
+    """32 values at scale 1 (amax 256 -> e = 0): exact e4m3 midpoints of
+    every spacing down to the subnormals, both signs; ties go to even."""
+    mids = [17, 19, 21, 23, 34, 38, 68, 76, 136, 152, 1.0625, 1.1875, 2.125, 2.375,
+            0.5 * 2 ** -9, 1.5 * 2 ** -9, 2.5 * 2 ** -9, 4.5 * 2 ** -9, 7.5 * 2 ** -9,
+            2.0 ** -6 + 2.0 ** -10]
+    vals = [256.0] + mids + [-m for m in mids[:11]]
+    assert len(vals) == 32
+    return torch.tensor(vals, dtype=torch.float64)
+
+
+def mx_special_blocks(gen) -> list:
+    """(name, 32 bf16 values) blocks for quant_mxfp8's edges."""
+    out = []
+
+    def planted(name, amax, pos=0, neg=False, frac=0.5):
+        b = _fill(gen, amax, 32, frac)
+        b[pos] = -amax if neg else amax
+        assert float(b[pos].double().abs()) == amax, f"{name}: amax is not a bf16 value"
+        out.append((name, b))
+
+    for j in (-20, 0, 9, 30):
+        edge = 0.875 * 2.0 ** j      # m == 0.875: amax 2^-e == 448, no step
+        planted(f"0.875*2^{j}", edge, pos=5)
+        planted(f"0.875*2^{j}+ulp", _bf16_step(edge, True), pos=31, neg=True)
+        planted(f"0.875*2^{j}-ulp", _bf16_step(edge, False), pos=0)
+        planted(f"2^{j}", 2.0 ** j, pos=17)
+        planted(f"2^{j}-ulp", _bf16_step(2.0 ** j, False), pos=16, neg=True)
+    unit = 2.0 ** -133               # bf16 subnormal spacing
+    b = (torch.randint(-3, 4, (32,), generator=gen).double() * unit).to(BF16)
+    b[9] = 5 * unit
+    out.append(("subnormal", b))
+    b = (torch.randint(-100, 101, (32,), generator=gen).double() * 2.0 ** -140)
+    b = b.to(BF16)                   # rounds to multiples of 2^-133, mostly 0
+    b[3] = -unit
+    out.append(("smallest subnormal", b))
+    planted("bf16 max", float(torch.finfo(BF16).max), pos=30, frac=2.0 ** -7)
+    planted("bf16 max, full block", float(torch.finfo(BF16).max), pos=1, neg=True, frac=1.0)
+    out.append(("zero block", torch.zeros(32, dtype=BF16)))
+    for p in range(32):
+        planted(f"amax at {p}", 3.5 * 2.0 ** (p - 16), pos=p, neg=bool(p & 1), frac=0.25)
+    for j in (0, -9, 13):
+        b = (_midpoint_block() * 2.0 ** j).to(BF16)
+        assert torch.equal(b.double(), _midpoint_block() * 2.0 ** j)
+        out.append((f"midpoints*2^{j}", b))
+    return out
+
+
+def mx_quant_inputs(gen, rows: int, K: int) -> list:
+    """Inputs [rows, K] bf16 for quant_mxfp8: random blocks spanning 2^+-30
+    per block, every special block planted once (over as many calls as the
+    shape needs), and row 1 all zero when there are at least three rows."""
+    nblk = K // 32
+    specials = mx_special_blocks(gen)
+    zero_row = 1 if rows >= 3 else None
+    free = [(r, b) for r in range(rows) if r != zero_row for b in range(nblk)]
+    calls = []
+    for c0 in range(0, len(specials), len(free)):
+        x = torch.randn(rows, nblk, 32, generator=gen, dtype=torch.float64)
+        x = (x * _pow2(torch.randint(-30, 31, (rows, nblk, 1), generator=gen))).to(BF16)
+        perm = torch.randperm(len(free), generator=gen).tolist()
+        for i, (_, blk) in enumerate(specials[c0:c0 + len(free)]):
+            r, b = free[perm[i]]
+            x[r, b] = blk
+        if zero_row is not None:
+            x[zero_row] = 0
+        calls.append(x.reshape(rows, K))
+    return calls
+
+
+def quant_mxfp8_expect(x: torch.Tensor):
+    """(q bytes [rows, K], scale bytes [rows, K/32]) by the fp64 rule:
+    e = floor(log2 amax) - 8, + 1 if amax 2^-e > 448, clamped to [-127, 127];
+    a zero block has byte 0.  The scale is a power of two, so x 2^-e is exact
+    and q = RNE_e4m3 of the exact quotient."""
+    rows, K = x.shape
+    blk = x.cpu().double().view(rows, K // 32, 32)
+    amax = blk.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)
+    e = ex.long() - 1 - 8
+    e = e + (amax * _pow2(-e) > E4M3_MAX).long()
+    e = torch.where(amax > 0, e, torch.full_like(e, -127)).clamp(-127, 127)
+    quot = blk * _pow2(-e).unsqueeze(-1)
+    assert float(quot.abs().max()) <= E4M3_MAX
+    return e4m3_rne_bytes(quot).reshape(rows, K), (e + 127).to(torch.uint8)
+
+
+def check_quant_mxfp8(fn, rows, K, dev, gen):
+    """fn(x [rows, K] bf16) -> (q u8 [rows, K], s u8 [rows, K/32]): scale
+    bytes and payload bytes EQUAL to quant_mxfp8_expect."""
+    for c, x in enumerate(mx_quant_inputs(gen, rows, K)):
+        q, s = fn(x.to(dev))
+        q_exp, s_exp = quant_mxfp8_expect(x)
+        what = f"quant_mxfp8 rows={rows} K={K} call {c}"
+        assert_bytes_equal(s, s_exp, what + " scale")
+        assert_bytes_equal(q, q_exp, what + " payload")
+
+
+FP8_TIE_MARGIN = 4 * U_FP32   # two f32 roundings (1/s and x * (1/s)), relative
+FP8_TIE_CAP = 1e-3            # share of a call's elements that may sit that close
+
+
+def fp8_amax_positions(K: int) -> list:
+    """Where the row maximum is planted: first / last element, the first and
+    last element of each wave's share of the first pass (thread t takes
+    vector t, so wave w covers elements [512 w, 512 w + 512)), and the
+    vectors past 256 (thread 0's second pass: element 2048 at K = 2056)."""
+    cand = [0, K - 1, K - 8]
+    for w in range(4):
+        cand += [512 * w, 512 * w + 511]
+    cand += [2048, 2055]
+    return sorted({p for p in cand if 0 <= p < K})
+
+
+def _fp8_random_row(gen, K: int, pos=None) -> torch.Tensor:
+    """randn clipped to +-3.9, the maximum (1 + odd/128) * 4 in [4, 8)
+    planted at ``pos`` (odd significand: x 448 / amax never lands exactly
+    on an e4m3 midpoint), all times 2^j."""
+    r = torch.randn(K, generator=gen, dtype=torch.float64).clamp(-3.9, 3.9)
+    odd = 2 * int(torch.randint(0, 64, (1,), generator=gen)) + 1
+    if pos is None:
+        pos = int(torch.randint(0, K, (1,), generator=gen))
+    sign = -1.0 if int(torch.randint(0, 2, (1,), generator=gen)) else 1.0
+    r[pos] = sign * (1 + odd / 128) * 4
+    j = int(torch.randint(-10, 11, (1,), generator=gen))
+    return (r * 2.0 ** j).to(BF16)
+
+
+def _fp8_exact_row(gen, K: int, j: int) -> torch.Tensor:
+    """amax = 448 * 2^j (scale 2^j and its inverse exact); every element an
+    e4m3 value or the exact midpoint of two neighbours, times 2^j."""
+    v = all_e4m3_magnitudes()
+    pool = torch.cat([v, (v[:-1] + v[1:]) / 2])
+    r = pool[torch.randint(0, pool.numel(), (K,), generator=gen)]
+    r = r * (torch.randint(0, 2, (K,), generator=gen).double() * 2 - 1)
+    r[int(torch.randint(0, K, (1,), generator=gen))] = E4M3_MAX
+    row = (r * 2.0 ** j).to(BF16)
+    assert torch.equal(row.double(), r * 2.0 ** j), "generator: not bf16 values"
+    return row
+
+
+def fp8_near_midpoint(x: torch.Tensor, s_ref: torch.Tensor) -> torch.Tensor:
+    """Elements whose x / s lies within FP8_TIE_MARGIN (relative) of the
+    midpoint of its two e4m3 neighbours (bool [rows, K])."""
+    a = (x.cpu().double() / s_ref.double().unsqueeze(1)).abs().clamp(max=E4M3_MAX)
+    lo, hi = e4m3_neighbours(a)
+    mid = (lo + hi) / 2
+    return (a - mid).abs() <= FP8_TIE_MARGIN * mid
+
+
+def quant_fp8_scale_ref(x: torch.Tensor) -> torch.Tensor:
+    """f32 amax / 448 (one correctly rounded division); 1 for a zero row."""
+    amax = x.cpu().float().abs().amax(dim=-1)
+    return torch.where(amax > 0, amax / torch.tensor(448.0), torch.ones_like(amax))
+
+
+def fp8_quant_inputs(gen, rows: int, K: int) -> list:
+    """[(x [rows, K] bf16, exact [rows] bool)]: amax planted at every
+    fp8_amax_positions(K), exact rows (amax 448 * 2^j), a zero row and random
+    rows, over as many calls as the shape needs.  Outside the exact rows at
+    most FP8_TIE_CAP of a call's elements lie near a midpoint (a call is
+    redrawn until that holds — the premise of the nearest-neighbour rule)."""
+    recipes = [("pos", p) for p in fp8_amax_positions(K)]
+    recipes += [("exact", j) for j in (-3, 0, 5)] + [("zero", None)]
+    recipes += [("random", None)] * 4
+    while len(recipes) % rows:
+        recipes.append(("random", None))
+    calls = []
+    for c0 in range(0, len(recipes), rows):
+        for _ in range(20):
+            xs, exact = [], []
+            for kind, arg in recipes[c0:c0 + rows]:
+                exact.append(kind == "exact")
+                if kind == "pos":
+                    xs.append(_fp8_random_row(gen, K, arg))
+                elif kind == "exact":
+                    xs.append(_fp8_exact_row(gen, K, arg))
+                elif kind == "zero":
+                    xs.append(torch.zeros(K, dtype=BF16))
+                else:
+                    xs.append(_fp8_random_row(gen, K))
+            x, exact = torch.stack(xs), torch.tensor(exact)
+            near = fp8_near_midpoint(x, quant_fp8_scale_ref(x))[~exact]
+            if int(near.sum()) <= int(FP8_TIE_CAP * x.numel()):
+                break
+        else:
+            raise AssertionError("generator: too many elements near a midpoint")
+        calls.append((x, exact))
+    return calls
+
+
+def judge_quant_fp8(x, exact, q, s, what="quant_fp8"):
+    """The contract of check_quant_fp8 on one call's result (CPU tensors)."""
+    x, q, s = x.cpu(), q.detach().cpu(), s.detach().cpu()
+    rows, K = x.shape
+    assert q.dtype == torch.uint8 and tuple(q.shape) == (rows, K), what
+    assert s.dtype == torch.float32 and tuple(s.shape) == (rows,), what
+    s_ref = quant_fp8_scale_ref(x)
+    if not torch.equal(s.view(torch.int32), s_ref.view(torch.int32)):
+        i = int((s.view(torch.int32) != s_ref.view(torch.int32)).nonzero()[0])
+        raise AssertionError(f"{what}: scale of row {i} is {float(s[i])!r}, "
+                             f"f32 amax/448 is {float(s_ref[i])!r}")
+    t = x.double() / s_ref.double().unsqueeze(1)
+    a = t.abs().clamp(max=E4M3_MAX)
+    lo, hi = e4m3_neighbours(a)
+    mid = (lo + hi) / 2
+    g = e4m3_to_f64(q & 0x7f)                      # NaN code 0x7f -> NaN: fails below
+    in_pair = (g == lo) | (g == hi)
+    nearest = torch.where(a < mid, lo, hi)
+    near_mid = fp8_near_midpoint(x, s_ref)
+    ok = in_pair & ((g == nearest) | near_mid) & ((q >> 7).bool() == torch.signbit(x))
+    if not bool(ok.all()):
+        i = tuple(int(v) for v in (~ok).nonzero()[0])
+        raise AssertionError(f"{what}: {int((~ok).sum())} elements wrong; first at {i}: "
+                             f"x/s = {float(t[i])!r}, got byte 0x{int(q[i]):02x} "
+                             f"({float(g[i])!r}), neighbours {float(lo[i])!r} / {float(hi[i])!r}")
+    free = ~exact.unsqueeze(1)
+    cap = int(FP8_TIE_CAP * x.numel())
+    assert int((near_mid & free).sum()) <= cap, f"{what}: generator premise (tie cap)"
+    assert int((near_mid & free & (g != nearest)).sum()) <= cap
+    if bool(exact.any()):   # scale and quotient exact: one rounding, ties to even
+        assert_bytes_equal(q[exact], e4m3_rne_bytes(t[exact]), what + " exact rows")
+
+
+def check_quant_fp8(fn, rows, K, dev, gen):
+    """fn(x [rows, K] bf16) -> (q u8 [rows, K], s f32 [rows]).
+    * s == f32 amax / 448 bit for bit (1 for an all-zero row);
+    * q is one of the two e4m3 neighbours of x / s (fp64, reference scale),
+      with x's sign, and the nearer one unless x / s lies within 4 * 2^-24
+      relative of their midpoint (the kernel multiplies by a rounded 1 / s:
+      two f32 roundings); at most 0.1% of a call's elements lie that close;
+    * rows with amax = 448 * 2^j: bytes equal RNE of the exact quotient."""
+    for c, (x, exact) in enumerate(fp8_quant_inputs(gen, rows, K)):
+        q, s = fn(x.to(dev))
+        judge_quant_fp8(x, exact, q, s, f"quant_fp8 rows={rows} K={K} call {c}")
+
+
+# --------------------------------------------------------------------------
+# MoE combine.  ``fn(down [P,H] bf16, pos [T,k] i32, weight [P] f32) -> [T,H]``
+# --------------------------------------------------------------------------
+def make_combine_case(gen, T, k, H, mode, pad=5):
+    """pos = a true inverse routing permutation: the T*k routed rows sit at
+    distinct random slots of a padded layout of P = T*k + pad rows; the pad
+    rows carry weight 0 and loud data (64).  mode 'pow2': integer rows in
+    [-8, 8], weights 2^-3 .. 2^1 (every partial sum exact); 'random'."""
+    P = T * k + pad
+    slots = torch.randperm(P, generator=gen)
+    pos = slots[:T * k].reshape(T, k).to(torch.int32)
+    if mode == "pow2":
+        down = torch.randint(-8, 9, (P, H), generator=gen).to(BF16)
+        w = torch.exp2(torch.randint(-3, 2, (P,), generator=gen).float())
+    else:
+        down = rand_bf16(gen, P, H)
+        w = (torch.rand(P, generator=gen) + 0.05).float()
+    w[slots[T * k:]] = 0.0
+    down[slots[T * k:]] = 64.0
+    p = pos.long()
+    terms = w.double()[p].unsqueeze(-1) * down.double()[p]      # [T, k, H]
+    return down, pos, w, terms.sum(dim=1), terms.abs().sum(dim=1)
+
+
+def check_moe_combine(fn, T, k, H, dev, gen):
+    """Bit for bit with power-of-two weights on integer rows; within
+    2^-8 |ref| + k 2^-24 sum|w v| on random data."""
+    for mode in ("pow2", "random"):
+        down, pos, w, ref, absum = make_combine_case(gen, T, k, H, mode)
+        got = fn(down.to(dev), pos.to(dev), w.to(dev))
+        what = f"moe_combine {mode} T={T} k={k} H={H}"
+        if mode == "pow2":
+            assert_bits_equal(got, exact_bf16(ref), what)
+        else:
+            assert tuple(got.shape) == (T, H), what
+            assert_within(got, ref, U_BF16_OUT * ref.abs() + k * U_FP32 * absum, what)

@@ -1,5 +1,5 @@
-"""CPU checks of the decode-kernel and prefill-attention oracles
-(tests/kernel_oracles.py).
+"""CPU checks of the decode-kernel, prefill-attention and quantized GEMM /
+quantizer / MoE oracles (tests/kernel_oracles.py).
 
 Three things are established without a GPU:
 1. each fp64 oracle agrees with the existing fp32 reference in
@@ -140,10 +140,40 @@ def test_onehot_expectations_are_exact_bf16(gen, kind):
         assert bool(ko.is_pow2(torch.exp2(wargs[1].double() - 127)).all())
 
 
-@pytest.mark.parametrize("kind,K", [("bf16", 14336), ("bf16", 15360), ("fp8", 4096), ("mx", 4096)])
+@pytest.mark.parametrize("kind,K", [("bf16", 14336), ("bf16", 15360), ("fp8", 4096), ("mx", 4096),
+                                    ("qgemm-fp8", 640), ("qgemm-mx", 640), ("grouped", 192),
+                                    ("combine", 2056)])
 def test_integer_sums_stay_exact_in_fp32(gen, kind, K):
     """sum |x||w| (an upper bound on every partial sum in any order), in
-    units of the smallest scale 2^-3, stays below 2^24."""
+    units of the smallest scale 2^-3, stays below 2^24.  The tiled quantized
+    GEMM, grouped GEMM and combine generators: the same in their own units
+    (unscaled integers / 2^-4 / integers / 2^-3)."""
+    if kind.startswith("qgemm"):
+        q = kind[len("qgemm-"):]
+        args, a64, b64 = ko.make_qgemm_case(q, "int", gen, 130, 140, K)
+        assert ko.qgemm_int_premise(q, args, a64, b64) < 2 ** 24
+        unit = 1 if q == "fp8" else 16      # fp8: the accumulator is unscaled
+        for t in ((ko.e4m3_to_f64(args[0]), ko.e4m3_to_f64(args[2])) if q == "fp8"
+                  else (a64, b64)):
+            assert float(t.abs().max()) <= (4 if q == "fp8" else 16)
+        prod = a64 @ b64.t()
+        assert torch.equal(prod * 64 * unit, (prod * 64 * unit).round())
+        ko.exact_bf16(prod)
+        s = (torch.cat([args[1], args[3]]).double() if q == "fp8"
+             else torch.exp2(torch.cat([args[1], args[3]]).double() - 127))
+        assert bool(ko.is_pow2(s).all())
+        return
+    if kind == "grouped":
+        a, w, starts, ref64, absdot = ko.make_grouped_case(gen, [3, 0, 130], 128, K, "int")
+        assert float(absdot.max()) < 2 ** 24 and torch.equal(ref64, ref64.round())
+        ko.exact_bf16(ref64)
+        return
+    if kind == "combine":
+        down, pos, w, ref64, absum = ko.make_combine_case(gen, 7, 3, K, "pow2")
+        assert float(absum.max()) * 8 < 2 ** 24 and torch.equal(ref64 * 8, (ref64 * 8).round())
+        assert bool(ko.is_pow2(w[w != 0]).all())
+        ko.exact_bf16(ref64)
+        return
     (wargs, w64) = ko.make_weights(kind, gen, 12, K, "int")
     x = ko.int_x(gen, 16, K)
     assert float(x.double().abs().max()) <= 2
@@ -684,3 +714,357 @@ def test_uncompensated_defer_rejected_by_staircase(pgen, S, mode):
     'stair-7' the deferred tiles hold e^-7 of the weight, so the same slip
     moves the output by 1e-3 max|V|: no bf16-level bound can see it there.)"""
     _rejected(ko.check_prefill_random, attn_variant(tiled="bug"), mode, 1, 4, 2, S, CPU, pgen)
+
+
+# ---------------- 5. quantized GEMM, grouped GEMM, quantizers, MoE combine ----------------
+QGEMM_FN = {"fp8": ops.gemm_bt_fp8, "mx": ops.gemm_bt_mxfp8}
+QGEMM_SHAPES = [(128, 128, 128), (130, 140, 640), (17, 384, 256)]
+GROUPED_SIZES = [[0, 1, 127, 128, 129, 0, 300, 5], [0, 0, 0, 0, 0, 0, 0, 77], [130, 0, 0, 0],
+                 [128, 128]]
+QUANT_FP8_SHAPES = [(r, K) for r in (1, 3, 64) for K in (8, 64, 2048, 2056, 4096)]
+QUANT_MX_SHAPES = [(r, K) for r in (1, 3, 64) for K in (32, 64, 8192, 8224)]
+COMBINE_SHAPES = [(k, H) for k in (1, 2, 3) for H in (8, 264, 2048, 2056)]
+
+
+# ---- premises ----
+@pytest.mark.parametrize("K", [128, 256, 384, 640])
+def test_qgemm_probe_columns_cover_boundaries(K):
+    cols = ko.qgemm_probe_columns(K)
+    assert set(ko.probe_columns(K)) <= set(cols) and 0 in cols and K - 1 in cols
+    for step in (16, 32, 64, 128):
+        for b in range(step, K, step):
+            assert b - 1 in cols and b in cols
+    assert len(cols) <= 128                      # one 128-row tile probes them all
+    assert set(ko.qgemm_onehot_cols(128, K).tolist()) == set(cols)
+
+
+@pytest.mark.parametrize("kind", ["fp8", "mx"])
+@pytest.mark.parametrize("M,N,K", QGEMM_SHAPES)
+def test_qgemm_onehot_expectations_are_exact_bf16(gen, kind, M, N, K):
+    """C = a b 2^(..) is a finite, non-zero, NORMAL bf16 value everywhere."""
+    args, a64, b64 = ko.make_qgemm_case(kind, "onehot", gen, M, N, K)
+    assert int((args[0] != 0).sum()) == M and bool(((args[0] != 0).sum(dim=1) == 1).all())
+    c = a64 @ b64.t()
+    assert torch.equal(c.to(torch.bfloat16).double(), c)
+    assert bool(torch.isfinite(c).all())
+    assert float(c.abs().min()) >= 2.0 ** -126 and float(c.abs().max()) < 2.0 ** 127
+    s = (torch.cat([args[1], args[3]]).double() if kind == "fp8"
+         else torch.exp2(torch.cat([args[1], args[3]]).double() - 127))
+    assert bool(ko.is_pow2(s).all())
+
+
+@pytest.mark.parametrize("M,N,nblk", [(128, 128, 4), (1, 384, 20), (2560, 4352, 12)])
+def test_mx_probe_scale_patterns_are_distinct(gen, M, N, nblk):
+    """Any two blocks of a row carry different exponents; an A row differs
+    from every B row in every block (parity); one A row sits near byte
+    127 + 40 and one B row near 127 - 40."""
+    a_s, b_s = ko.mx_probe_scales(gen, M, N, nblk)
+    for s in (a_s, b_s):
+        srt = s.long().sort(dim=1).values
+        assert bool((srt[:, 1:] != srt[:, :-1]).all())
+    assert bool((a_s.long() % 2 == 1).all()) and bool((b_s.long() % 2 == 0).all())
+    assert int(a_s[min(1, M - 1)].min()) >= 127 + 40 - 32
+    assert int(a_s[min(1, M - 1)].max()) >= 127 + 40
+    assert int(b_s[min(2, N - 1)].max()) <= 127 - 40 + 32
+    assert int(b_s[min(2, N - 1)].min()) <= 127 - 40
+
+
+def test_e4m3_rne_bytes_is_round_to_nearest_even(gen):
+    v = ko.all_e4m3_magnitudes()
+    assert v.numel() == 127 and float(v[0]) == 0 and float(v[-1]) == 448
+    assert bool((v[1:] > v[:-1]).all())
+    codes = torch.arange(0, 0x7f, dtype=torch.uint8)
+    assert torch.equal(ko.e4m3_rne_bytes(v), codes)                       # identity
+    assert torch.equal(ko.e4m3_rne_bytes(-v), codes | 0x80)               # sign kept, -0 too
+    mids = (v[:-1] + v[1:]) / 2
+    even = torch.where(codes[:-1] % 2 == 0, codes[:-1], codes[1:])        # even code = even mantissa
+    assert torch.equal(ko.e4m3_rne_bytes(mids), even)
+    assert torch.equal(ko.e4m3_rne_bytes(mids * (1 + 2.0 ** -40)), codes[1:])
+    assert torch.equal(ko.e4m3_rne_bytes(mids * (1 - 2.0 ** -40)), codes[:-1])
+    assert int(ko.e4m3_rne_bytes(torch.tensor([463.9], dtype=torch.float64))) == 0x7e
+    # and it agrees with torch's conversion wherever that rounds an f32 once
+    x = (torch.randn(20000, generator=gen) * torch.exp2(torch.randint(-12, 8, (20000,), generator=gen)
+                                                         .float())).clamp(-448, 448)
+    assert torch.equal(ko.e4m3_rne_bytes(x.double()),
+                       x.to(torch.float8_e4m3fn).view(torch.uint8))
+    lo, hi = ko.e4m3_neighbours(torch.tensor([0.0, 17.0, 448.0, 2.0 ** -10, 15.9],
+                                             dtype=torch.float64))
+    assert lo.tolist() == [0.0, 16.0, 448.0, 0.0, 15.0]
+    assert hi.tolist() == [2.0 ** -9, 18.0, 480.0, 2.0 ** -9, 16.0]
+
+
+def test_mx_special_blocks_hit_the_edges(gen):
+    blocks = dict(ko.mx_special_blocks(gen))
+    assert len([n for n in blocks if n.startswith("amax at ")]) == 32
+
+    def byte(name):
+        return int(ko.quant_mxfp8_expect(blocks[name].reshape(1, 32))[1])
+
+    for j in (-20, 0, 9, 30):
+        assert byte(f"0.875*2^{j}") == j - 9 + 127        # amax 2^-e == 448 exactly
+        assert byte(f"0.875*2^{j}+ulp") == j - 8 + 127    # one ulp more: steps
+        assert byte(f"0.875*2^{j}-ulp") == j - 9 + 127
+        assert byte(f"2^{j}") == j - 8 + 127
+        assert byte(f"2^{j}-ulp") == j - 8 + 127          # floor gives j - 9, then the step
+        q, _ = ko.quant_mxfp8_expect(blocks[f"0.875*2^{j}"].reshape(1, 32))
+        assert int(q[0, 5]) == 0x7e                       # 448
+    assert byte("zero block") == 0 and byte("subnormal") == 0 and byte("bf16 max") == 247
+    q, _ = ko.quant_mxfp8_expect(blocks["subnormal"].reshape(1, 32))
+    assert float(ko.e4m3_to_f64(q)[0, 9]) == 5 * 2.0 ** -6   # clamped scale keeps the payload
+    for p in range(32):
+        b = blocks[f"amax at {p}"].double().abs()
+        assert int(b.argmax()) == p and float(b.sort().values[-2]) < float(b[p])
+    q, s = ko.quant_mxfp8_expect(blocks["midpoints*2^0"].reshape(1, 32))
+    assert int(s) == 127
+    got = ko.e4m3_to_f64(q)[0, 1:5].tolist()
+    assert got == [16.0, 20.0, 20.0, 24.0]                # 17 19 21 23: ties to even
+
+
+@pytest.mark.parametrize("rows,K", QUANT_MX_SHAPES)
+def test_mx_quant_inputs_plant_everything(gen, rows, K):
+    calls = ko.mx_quant_inputs(gen, rows, K)
+    nsp = len(ko.mx_special_blocks(gen))
+    free = (rows - (1 if rows >= 3 else 0)) * (K // 32)
+    assert len(calls) == -(-nsp // free)
+    x = torch.cat([c.reshape(-1, 32) for c in calls]).double()
+    amax = x.abs().amax(dim=1)
+    assert bool((amax == 0).any()) and float(amax.max()) == float(torch.finfo(torch.bfloat16).max)
+    assert bool(((amax > 0) & (amax < 2.0 ** -126)).any())            # subnormal block
+    if rows >= 3:
+        assert all(bool((c[1] == 0).all()) for c in calls)
+    if rows * (K // 32) > 2 * nsp:                                     # per-block range
+        nz = amax[amax > 0]
+        assert float(nz.max() / nz.min()) > 2.0 ** 60
+
+
+@pytest.mark.parametrize("rows,K", QUANT_FP8_SHAPES)
+def test_fp8_quant_tie_cap_holds_for_the_reference(gen, rows, K):
+    """At most 0.1% of a call's elements (exact rows aside) lie within
+    4 * 2^-24 of an e4m3 midpoint, so the reference needs no more excuses
+    than that; every planted position and each exact row is there."""
+    calls = ko.fp8_quant_inputs(gen, rows, K)
+    seen = set()
+    for x, exact in calls:
+        s_ref = ko.quant_fp8_scale_ref(x)
+        near = ko.fp8_near_midpoint(x, s_ref)
+        assert int(near[~exact].sum()) <= int(ko.FP8_TIE_CAP * x.numel())
+        seen.update(x.double().abs().argmax(dim=1)[x.double().abs().amax(dim=1) > 0].tolist())
+        for r in exact.nonzero().flatten().tolist():
+            assert bool(ko.is_pow2(s_ref[r])), "exact row: scale is a power of two"
+            t = x[r].double() / s_ref[r].double()
+            lo, hi = ko.e4m3_neighbours(t.abs())
+            assert bool(((t.abs() == lo) | (t.abs() == (lo + hi) / 2)).all())
+            assert bool((t.abs() == (lo + hi) / 2).any()) or K < 64
+    assert set(ko.fp8_amax_positions(K)) <= seen
+    assert sum(int(e.sum()) for _, e in calls) == 3
+    assert any(bool((x.double().abs().amax(dim=1) == 0).any()) for x, _ in calls)
+    if K == 2056:
+        assert {2048, 2055, 0, 511, 512, 1023, 1024, 1535, 1536, 2047} <= set(
+            ko.fp8_amax_positions(K))
+
+
+def test_grouped_and_combine_generators(gen):
+    a, w, starts, ref64, absdot = ko.make_grouped_case(gen, [0, 3, 130], 128, 64, "random")
+    assert starts == [0, 0, 3, 133] and a.shape == (133, 64) and w.shape == (3, 128, 64)
+    down, pos, wt, ref64, absum = ko.make_combine_case(gen, 7, 3, 264, "random")
+    P = 7 * 3 + 5
+    assert pos.unique().numel() == 21 and int(pos.max()) < P       # an injection
+    pads = sorted(set(range(P)) - set(pos.flatten().tolist()))
+    assert len(pads) == 5 and bool((wt[pads] == 0).all()) and bool((wt[pos.long()] > 0).all())
+    assert bool((down[pads] == 64).all())
+    assert not torch.equal(pos.flatten().long(), torch.arange(21))  # permuted
+
+
+# ---- the CPU fallbacks pass every new check ----
+@pytest.mark.parametrize("kind", ["fp8", "mx"])
+@pytest.mark.parametrize("M,N,K", QGEMM_SHAPES)
+def test_qgemm_cpu_fallback_passes(gen, kind, M, N, K):
+    ko.check_qgemm_onehot(QGEMM_FN[kind], kind, M, N, K, CPU, gen)
+    ko.check_qgemm_int(QGEMM_FN[kind], kind, M, N, K, CPU, gen)
+    # true fp32 sums need no kfactor (the GPU's is measured, QGEMM_KFACTOR)
+    assert ko.check_qgemm_random(QGEMM_FN[kind], kind, M, N, K, CPU, gen, kfactor=1) <= 1.0
+
+
+@pytest.mark.parametrize("sizes", GROUPED_SIZES)
+def test_grouped_gemm_cpu_fallback_passes(gen, sizes):
+    for N, K in ((128, 64), (384, 192)):
+        ko.check_grouped_gemm(ops.grouped_gemm_bt, sizes, N, K, CPU, gen)
+
+
+def test_grouped_gemm_rejects_offsets_past_the_rows(gen):
+    a, w = ko.rand_bf16(gen, 10, 64), ko.rand_bf16(gen, 2, 128, 64)
+    with pytest.raises(ValueError):
+        ops.grouped_gemm_bt(a, w, [0, 4, 11])
+    with pytest.raises(ValueError):
+        ops.grouped_gemm_bt(a, w, [0, 4])          # E + 1 offsets, no fewer
+    with pytest.raises(ValueError):
+        ops.grouped_gemm_bt(a, w, [0, 6, 4])
+    assert ops.grouped_gemm_bt(a, w, [0, 4, 10]).shape == (10, 128)
+
+
+@pytest.mark.parametrize("rows,K", QUANT_MX_SHAPES)
+def test_quant_mxfp8_cpu_fallback_passes(gen, rows, K):
+    ko.check_quant_mxfp8(ops.quant_mxfp8, rows, K, CPU, gen)
+
+
+@pytest.mark.parametrize("rows,K", QUANT_FP8_SHAPES)
+def test_quant_fp8_cpu_fallback_passes(gen, rows, K):
+    """quant_fp8_ref divides by the scale where the kernel multiplies by its
+    rounded inverse; the neighbour rule admits both."""
+    ko.check_quant_fp8(ops.quant_fp8, rows, K, CPU, gen)
+
+
+@pytest.mark.parametrize("k,H", COMBINE_SHAPES)
+def test_moe_combine_reference_passes(gen, k, H):
+    ko.check_moe_combine(ref.moe_combine_ref, 7, k, H, CPU, gen)
+
+
+# ---- mutants: each wrong operator is rejected by a named check ----
+def qgemm_mutant(kind, name):
+    """The CPU fallback with one property of the tiled kernels switched."""
+    def fn(a_q, a_s, b_q, b_s):
+        M, K = a_q.shape
+        N = b_q.shape[0]
+        if name == "drop_last_tile":              # the K loop ends one tile early
+            a_q = a_q.clone()
+            a_q[:, K - 128:] = 0
+        elif name == "stale_last_scales":         # na / nb never copied for the last tile
+            a_s, b_s = a_s.clone(), b_s.clone()
+            a_s[:, -4:], b_s[:, -4:] = a_s[:, -8:-4].clone(), b_s[:, -8:-4].clone()
+        elif name == "swap_lhi":                  # the lane halves' blocks exchanged
+            a_s = a_s.view(M, -1, 2).flip(-1).reshape(M, -1)
+            b_s = b_s.view(N, -1, 2).flip(-1).reshape(N, -1)
+        elif name == "swap_halves":               # kk = 0 / 1 scale pairs exchanged
+            a_s = a_s.view(M, -1, 2, 2).flip(-2).reshape(M, -1)
+            b_s = b_s.view(N, -1, 2, 2).flip(-2).reshape(N, -1)
+        elif name == "a_s_by_column":             # epilogue reads a_s[col]
+            af = a_q.view(torch.float8_e4m3fn).float()
+            bf = b_q.view(torch.float8_e4m3fn).float()
+            return ((af @ bf.t()) * a_s[torch.arange(N) % M].unsqueeze(0)
+                    * b_s.unsqueeze(0)).to(torch.bfloat16)
+        elif name == "swizzle_row_plus1":         # A's LDS chunk XOR taken from row + 1
+            r = torch.arange(M)
+            x = (r & 7) ^ ((r + 1) & 7)
+            c = torch.arange(8).unsqueeze(0) ^ x.unsqueeze(1)           # [M, 8]
+            idx = c.view(M, 1, 8, 1).expand(M, K // 128, 8, 16)
+            a_q = a_q.view(M, K // 128, 8, 16).gather(2, idx).reshape(M, K)
+        else:
+            raise ValueError(name)
+        return QGEMM_FN[kind](a_q, a_s, b_q, b_s)
+    return fn
+
+
+QG = (130, 140, 384)
+
+
+@pytest.mark.parametrize("kind", ["fp8", "mx"])
+def test_dropped_last_k_tile_rejected(gen, kind):
+    bad = qgemm_mutant(kind, "drop_last_tile")
+    _rejected(ko.check_qgemm_onehot, bad, kind, *QG, CPU, gen)
+    _rejected(ko.check_qgemm_int, bad, kind, *QG, CPU, gen)
+    _rejected(ko.check_qgemm_random, bad, kind, *QG, CPU, gen)
+
+
+def test_stale_last_tile_scales_rejected(gen):
+    bad = qgemm_mutant("mx", "stale_last_scales")
+    _rejected(ko.check_qgemm_onehot, bad, "mx", *QG, CPU, gen)
+    _rejected(ko.check_qgemm_random, bad, "mx", *QG, CPU, gen)
+    _rejected(ko.check_qgemm_onehot, bad, "mx", 128, 128, 256, CPU, gen)
+
+
+@pytest.mark.parametrize("name", ["swap_lhi", "swap_halves"])
+@pytest.mark.parametrize("K", [128, 384])
+def test_swapped_mx_scale_blocks_rejected(gen, name, K):
+    _rejected(ko.check_qgemm_onehot, qgemm_mutant("mx", name), "mx", 128, 128, K, CPU, gen)
+
+
+def test_a_scale_indexed_by_column_rejected(gen):
+    bad = qgemm_mutant("fp8", "a_s_by_column")
+    _rejected(ko.check_qgemm_onehot, bad, "fp8", *QG, CPU, gen)
+    _rejected(ko.check_qgemm_int, bad, "fp8", *QG, CPU, gen)
+    _rejected(ko.check_qgemm_random, bad, "fp8", *QG, CPU, gen)
+
+
+@pytest.mark.parametrize("kind", ["fp8", "mx"])
+def test_chunk_swizzle_off_by_one_row_rejected(gen, kind):
+    bad = qgemm_mutant(kind, "swizzle_row_plus1")
+    _rejected(ko.check_qgemm_onehot, bad, kind, *QG, CPU, gen)
+    _rejected(ko.check_qgemm_int, bad, kind, *QG, CPU, gen)
+
+
+def grouped_mutant(name):
+    def fn(a, w, seg):
+        starts, E = list(seg), w.shape[0]
+        if name == "expert_plus1":                # a tile takes its neighbour's weights
+            return ops.grouped_gemm_bt(a, torch.roll(w, -1, 0), seg)
+        out = ops.grouped_gemm_bt(a, w, seg)
+        if name == "mask_gt":                     # row == seg_end stored by the tile before it
+            for e in range(E):
+                s, t = starts[e], starts[e + 1]
+                if t > s and (t - s) % 128 and t < a.shape[0]:
+                    out[t] = ref.gemm_bt_ref(a[t:t + 1], w[e])
+        return out
+    return fn
+
+
+@pytest.mark.parametrize("name", ["mask_gt", "expert_plus1"])
+@pytest.mark.parametrize("sizes", [GROUPED_SIZES[0], [130, 0, 0, 5]])
+def test_grouped_gemm_mutants_rejected(gen, name, sizes):
+    _rejected(ko.check_grouped_gemm, grouped_mutant(name), sizes, 128, 64, CPU, gen)
+
+
+def test_mx_scale_without_the_step_rejected(gen):
+    def floor_only(x):                            # OCP floor - 8, saturating
+        blk = x.float().view(x.shape[0], -1, 32)
+        amax = blk.abs().amax(dim=-1)
+        e = torch.where(amax > 0, torch.frexp(amax)[1].float() - 9,
+                        torch.full_like(amax, -127.0)).clamp(-127, 127)
+        q = (blk * torch.exp2(-e).unsqueeze(-1)).clamp(-448, 448)
+        return (q.to(torch.float8_e4m3fn).view(torch.uint8).reshape(x.shape),
+                (e + 127).to(torch.uint8))
+
+    for rows, K in ((1, 32), (3, 64), (64, 8224)):
+        _rejected(ko.check_quant_mxfp8, floor_only, rows, K, CPU, gen)
+
+
+def test_fp8_quant_mutants_rejected(gen):
+    def truncating(x):                            # round toward zero
+        q, s = ref.quant_fp8_ref(x)
+        t = (x.float() / s.unsqueeze(1)).double()
+        lo, _ = ko.e4m3_neighbours(t.abs().clamp(max=448))
+        return ko._e4m3_encode(lo, torch.signbit(t)), s
+
+    def scale_by_reciprocal(x):                   # amax * (1 / 448): not amax / 448
+        q, s = ref.quant_fp8_ref(x)
+        amax = x.float().abs().amax(dim=-1)
+        return q, torch.where(amax > 0, amax * (torch.tensor(1.0) / 448.0), s)
+
+    def off_by_one_code(x):                       # the farther neighbour, one element
+        q, s = ref.quant_fp8_ref(x)
+        q = q.clone()
+        big = x.double().abs().argmax(dim=1)      # the row maximum: code 0x7e
+        q[0, big[0]] -= 1
+        return q, s
+
+    for rows, K in ((1, 64), (3, 2056), (64, 4096)):
+        _rejected(ko.check_quant_fp8, truncating, rows, K, CPU, gen)
+        _rejected(ko.check_quant_fp8, off_by_one_code, rows, K, CPU, gen)
+    _rejected(ko.check_quant_fp8, scale_by_reciprocal, 64, 64, CPU, gen)
+
+
+@pytest.mark.parametrize("k,H", COMBINE_SHAPES)
+def test_combine_ignoring_last_term_rejected(gen, k, H):
+    def bad(down, pos, weight):
+        if k == 1:
+            return torch.zeros(pos.shape[0], H, dtype=torch.bfloat16)
+        return ref.moe_combine_ref(down, pos[:, :k - 1], weight)
+
+    _rejected(ko.check_moe_combine, bad, 7, k, H, CPU, gen)
+
+
+def test_combine_using_a_pad_row_rejected(gen):
+    def bad(down, pos, weight):                   # weight taken by position, not by slot
+        w = torch.ones_like(weight)
+        return ref.moe_combine_ref(down, pos, w)
+
+    _rejected(ko.check_moe_combine, bad, 7, 2, 264, CPU, gen)
