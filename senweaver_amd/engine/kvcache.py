@@ -53,6 +53,21 @@ class PagedKVCache:
         self.block_tables[seq] = []
         self.seq_lens[seq] = 0
 
+    def truncate(self, seq: int, new_len: int) -> None:
+        """Roll sequence ``seq`` back to its first ``new_len`` positions.
+        Pages wholly beyond ceil(new_len / 16) return to the free list; the
+        last kept page keeps its stale tail, which no kernel reads (every
+        reader stops at the logical length)."""
+        if not 0 <= new_len <= self.seq_lens[seq]:
+            raise ValueError(
+                f"truncate: new_len {new_len} outside [0, {self.seq_lens[seq]}] "
+                f"for seq {seq}")
+        keep = (new_len + PAGE_SIZE - 1) // PAGE_SIZE
+        bt = self.block_tables[seq]
+        self._free.extend(reversed(bt[keep:]))
+        del bt[keep:]
+        self.seq_lens[seq] = new_len
+
     def slot_ids(self, seq: int, start: int, count: int) -> torch.Tensor:
         """Flat slot index (page*16 + off) for positions [start, start+count)."""
         bt = self.block_tables[seq]

@@ -16,6 +16,7 @@ negative-reward ones score higher.
 
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -39,7 +40,8 @@ def _pad64(n: int) -> int:
 class LlamaBackend:
     def __init__(self, config: ModelConfig | str = "llama-3-8b", device: Optional[str] = None,
                  seed: int = 0, max_seq: int = 2048, micro_batch: int = 8, tp=None, quant: str = "bf16",
-                 prefix_pack: bool = True) -> None:
+                 prefix_pack: bool = True,
+                 prefix_cache: Optional[bool] = None) -> None:
         if isinstance(config, str):
             config = get_config(config)
         if device is None:
@@ -54,6 +56,18 @@ class LlamaBackend:
         # a microbatch (the candidate prompt, in score_batch's candidate-major
         # order) is computed once instead of once per rollout
         self.prefix_pack = prefix_pack
+        # prefix caching across generate() calls: keep the paged KV cache of
+        # the previous call and prefill only the tokens past the longest
+        # common prefix (a conversation's turn k+1 is turn k plus a few
+        # messages).  None reads SENWEAVER_PREFIX_CACHE ("1" = on); off by
+        # default.
+        if prefix_cache is None:
+            prefix_cache = os.environ.get("SENWEAVER_PREFIX_CACHE", "0") == "1"
+        self.prefix_cache = bool(prefix_cache)
+        # token ids whose K/V sit in the decode cache (sequence 0), or None
+        self._cached_ids: Optional[List[int]] = None
+        self._pc_stats = {"calls": 0, "hits": 0, "tokens_reused": 0,
+                          "tokens_prefilled": 0}
 
     # ------------------------------------------------------------------
     # Sequence building
@@ -266,8 +280,63 @@ class LlamaBackend:
         real = len(ids)
         # decode steps can never push past the cache (+2 slack pages)
         max_new_tokens = max(1, min(max_new_tokens, self.max_seq - real))
-        S = _pad64(real)
         cache, graph = self._decode_state()
+        # every id whose K/V reach the cache, in order: the prompt, then each
+        # generated token that goes through a decode step
+        all_ids = list(ids)
+        try:
+            last_hidden = self._prefill_prompt(cache, ids)
+        except BaseException:
+            self._cached_ids = None   # cache state unknown: next call resets
+            raise
+        seq = 0
+        try:
+            return self._decode_loop(
+                cache, graph, seq, last_hidden, all_ids, max_new_tokens,
+                should_stop, on_chunk, temperature, top_p, sample_seed, stop,
+                presence_penalty, frequency_penalty, logit_bias)
+        finally:
+            if self.prefix_cache:
+                # whatever ended the call (stop, abort, exception, EOS): what
+                # is cached is what the cache's logical length covers
+                self._cached_ids = all_ids[:cache.seq_lens[seq]]
+
+    def prefix_cache_stats(self) -> dict:
+        """calls / hits / tokens_reused / tokens_prefilled of stream_generate
+        since construction (real tokens; padding is not counted)."""
+        return dict(self._pc_stats)
+
+    def _prefill_prompt(self, cache, ids: List[int]) -> torch.Tensor:
+        """K/V of ``ids`` into sequence 0 of the decode cache; returns the
+        hidden state of the last position.  With prefix caching on, the
+        longest common prefix with the previous call's cached ids is kept
+        and only the rest goes through the model (prefill_extend)."""
+        real = len(ids)
+        st = self._pc_stats
+        st["calls"] += 1
+        m = 0
+        cached = self._cached_ids if self.prefix_cache else None
+        self._cached_ids = None  # rebuilt when the call ends
+        if cached and len(cache.seq_lens) == 1 and cache.seq_lens[0] == len(cached):
+            lim = min(len(cached), real - 1)  # the last position is computed
+            while m < lim and cached[m] == ids[m]:
+                m += 1
+        if m > 0:
+            seq = 0
+            cache.truncate(seq, m)
+            n = real - m
+            # 64-row granularity bounds the distinct GEMM row counts (each
+            # is a tuning key of its own) at max_seq / 64
+            Sq = (n + 63) & ~63
+            tokens = torch.zeros(1, Sq, dtype=torch.long)
+            tokens[0, :n] = torch.tensor(ids[m:], dtype=torch.long)
+            hidden = self.model.prefill_extend(tokens.to(self.device), cache,
+                                               [seq], [n])
+            st["hits"] += 1
+            st["tokens_reused"] += m
+            st["tokens_prefilled"] += n
+            return hidden[0, n - 1]
+        S = _pad64(real)
         # full reset (also recovers pages leaked by an aborted prefill)
         cache._free = list(range(cache.num_pages - 1, -1, -1))
         cache.block_tables, cache.seq_lens = [], []
@@ -276,7 +345,13 @@ class LlamaBackend:
         tokens[0, :real] = torch.tensor(ids, dtype=torch.long)
         hidden = self.model.prefill(tokens.to(self.device), cache=cache, seqs=[seq],
                                     real_lens=[real])
-        last_hidden = hidden[0, real - 1]
+        st["tokens_prefilled"] += real
+        return hidden[0, real - 1]
+
+    def _decode_loop(self, cache, graph, seq, last_hidden, all_ids,
+                     max_new_tokens, should_stop, on_chunk, temperature, top_p,
+                     sample_seed, stop, presence_penalty, frequency_penalty,
+                     logit_bias) -> str:
         out_ids = []
         text = ""
         gen = None
@@ -316,6 +391,7 @@ class LlamaBackend:
                     on_chunk(text)
                     break
             on_chunk(text)
+            all_ids.append(nxt)
             last_hidden = self._decode_one(cache, graph, seq, nxt)
         return text
 

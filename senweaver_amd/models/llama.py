@@ -622,6 +622,77 @@ class LlamaModel:
         h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
         return h  # [B, hidden]
 
+    # ------------------------------------------------------------------
+    # Extend: append new_lens[b] tokens to sequences that already hold
+    # cache.seq_lens[seq] positions.  tokens [B, Sq] (rows padded to Sq)
+    # -> final hidden states [B, Sq, H]; pad rows carry no meaning.
+    # ------------------------------------------------------------------
+    def prefill_extend(self, tokens: torch.Tensor, cache, seqs: List[int],
+                       new_lens: List[int]) -> torch.Tensor:
+        """Prefill of a suffix against the paged cache: the new tokens'
+        K/V go straight into their cache slots (rope_kv_append, real rows
+        only: a pad row writes no slot and needs no rope position), then
+        paged_prefill_attn reads history and new keys alike through the
+        block table.  seq_lens advance once, after the last layer."""
+        c = self.config
+        B, Sq = tokens.shape
+        assert len(seqs) == B and len(new_lens) == B
+        starts = [cache.seq_lens[s] for s in seqs]
+        for b in range(B):
+            if not 1 <= new_lens[b] <= Sq:
+                raise ValueError(f"prefill_extend: new_lens[{b}]={new_lens[b]} "
+                                 f"outside [1, {Sq}]")
+            if starts[b] + new_lens[b] > c.max_position:
+                raise ValueError("prefill_extend: past the rope table")
+            cache._ensure_capacity(seqs[b], starts[b] + new_lens[b])
+        dev = self.device
+        pos32 = torch.cat([torch.arange(starts[b], starts[b] + new_lens[b],
+                                        dtype=torch.int32) for b in range(B)]).to(dev)
+        slot = torch.cat([cache.slot_ids(seqs[b], starts[b], new_lens[b])
+                          for b in range(B)]).to(torch.int32)
+        # flat rows of the real tokens; None when there is no pad row
+        real_idx = None
+        if any(n != Sq for n in new_lens):
+            real_idx = torch.cat([torch.arange(b * Sq, b * Sq + new_lens[b])
+                                  for b in range(B)]).to(dev)
+        bt = cache.block_table_tensor(seqs)
+        ctx = torch.tensor([starts[b] + new_lens[b] for b in range(B)],
+                           dtype=torch.int32, device=dev)
+        qlen = torch.tensor(new_lens, dtype=torch.int32, device=dev)
+
+        hidden = self.embed[tokens.reshape(B * Sq).long()]
+        residual = None
+        Hq, Hk, D = self.local_heads, self.local_kv_heads, c.head_dim
+        for li, L in enumerate(self.layers):
+            if residual is None:
+                residual = hidden.clone()
+                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
+            else:
+                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
+            qkv = self._linear(h, L, "qkv")
+            P = cache.k[li].shape[0]
+            q_real = ops.rope_kv_append(
+                qkv if real_idx is None else qkv[real_idx],
+                self.cos_sin, pos32, slot,
+                cache.k[li].view(P * 16, Hk, D), cache.v[li].view(P * 16, Hk, D),
+                Hq, Hk, D)
+            if real_idx is None:
+                q = q_real.reshape(B, Sq, Hq, D)
+            else:
+                q = q_real.new_zeros(B * Sq, Hq, D)
+                q[real_idx] = q_real
+                q = q.reshape(B, Sq, Hq, D)
+            attn = ops.paged_prefill_attn(q, cache.k[li], cache.v[li], bt, ctx,
+                                          qlen, self.scale)
+            o = self._linear(attn.reshape(B * Sq, self.local_q_size), L, "o")
+            self.tp.all_reduce_(o)
+            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
+            hidden = self._ffn(h, L)
+        for b in range(B):
+            cache.seq_lens[seqs[b]] = starts[b] + new_lens[b]
+        h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
+        return h.reshape(B, Sq, c.hidden_size)
+
     def logits(self, hidden: torch.Tensor) -> torch.Tensor:
         """hidden [*, H] -> logits [*, vocab] through the lm_head GEMM."""
         flat = hidden.reshape(-1, self.config.hidden_size)

@@ -676,6 +676,25 @@ def paged_decode_attn(q, kcache, vcache, block_table, ctx_lens, scale: Optional[
     return ref.paged_decode_attn_ref(q, kcache, vcache, block_table, ctx_lens, scale)
 
 
+def paged_prefill_attn(q, kcache, vcache, block_table, ctx_lens, q_lens,
+                       scale: Optional[float] = None):
+    """Prefill attention over the paged cache with the queries at an offset.
+
+    q [B, Sq, H, 128]: the q_lens[b] NEW tokens of sequence b (token-major,
+    as rope_kv_append leaves them); their K/V are already in the caches
+    [P, 16, Hk, 128] and ctx_lens[b] counts them.  Row i attends to
+    positions 0 .. ctx_lens[b] - q_lens[b] + i.  Returns o in q's layout, so
+    o.reshape(B*Sq, H*D) feeds o_proj; rows i >= q_lens[b] are zero."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q):
+        return hip_ext().paged_prefill_attn(
+            q.contiguous(), kcache, vcache, block_table.to(torch.int32),
+            ctx_lens.to(torch.int32), q_lens.to(torch.int32), scale)
+    return ref.paged_prefill_attn_ref(q, kcache, vcache, block_table, ctx_lens,
+                                      q_lens, scale)
+
+
 def argmax_rows(logits: torch.Tensor) -> torch.Tensor:
     if _on_gpu(logits):
         return hip_ext().argmax_rows(logits.contiguous())

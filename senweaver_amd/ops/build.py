@@ -20,7 +20,8 @@ SOURCES = [
     for f in ("bindings.hip", "elemwise.hip", "sampling.hip", "gemm.hip",
               "gemm_pipe.hip", "gemm_asm.hip", "attention.hip", "attention_v2.hip",
               "attention_v4.hip", "gemm_lt.hip",
-              "decode_attention.hip", "moe.hip", "fp8.hip")
+              "decode_attention.hip", "paged_prefill_attention.hip", "moe.hip",
+              "fp8.hip")
 ]
 
 

@@ -79,6 +79,9 @@ extern "C" __global__ void attn_fwd_v3_kernel(const ushort*, const ushort*, cons
 extern "C" __global__ void paged_decode_attn_partial_kernel(const ushort*, const ushort*, const ushort*, float*,
                                                             const int*, const int*, int, int, int, float);
 extern "C" __global__ void paged_decode_attn_merge_kernel(const float*, ushort*, int);
+extern "C" __global__ void paged_prefill_attn_kernel(const ushort*, const ushort*, const ushort*, ushort*,
+                                                     const int*, const int*, const int*,
+                                                     int, int, int, int, float);
 
 namespace {
 
@@ -831,6 +834,43 @@ torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor kcache,
   return o;
 }
 
+// ---------------- Paged-context prefill attention ----------------
+// q [B, Sq, H, 128]: the q_lens[b] new tokens of sequence b, whose K/V are
+// already in the cache; ctx_lens[b] counts them.  o has q's layout, pad rows
+// (i >= q_lens[b]) zero.
+torch::Tensor paged_prefill_attn(torch::Tensor q, torch::Tensor kcache,
+                                 torch::Tensor vcache, torch::Tensor block_table,
+                                 torch::Tensor ctx_lens, torch::Tensor q_lens,
+                                 double scale) {
+  check_bf16(q, "q");
+  check_bf16(kcache, "kcache");
+  check_bf16(vcache, "vcache");
+  TORCH_CHECK(q.dim() == 4, "q must be [B, Sq, H, D]");
+  TORCH_CHECK(kcache.dim() == 4 && vcache.sizes() == kcache.sizes(),
+              "caches must be [P, 16, Hk, D] and alike");
+  for (const torch::Tensor* t : {&block_table, &ctx_lens, &q_lens})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt32 && t->is_contiguous(),
+                "block_table / ctx_lens / q_lens must be contiguous int32 on GPU");
+  const int B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  const int Hk = kcache.size(2);
+  TORCH_CHECK(D == 128 && kcache.size(3) == D, "D must be 128");
+  TORCH_CHECK(kcache.size(1) == 16, "PAGE_SIZE=16");
+  TORCH_CHECK(Sq >= 1 && B >= 1 && Hk >= 1 && H % Hk == 0);
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1 && ctx_lens.numel() == B &&
+              q_lens.numel() == B, "block_table / ctx_lens / q_lens: B mismatch");
+  // the kernel keeps a block-table row in LDS (PP_MAX_PAGES entries)
+  TORCH_CHECK(block_table.size(1) <= 2048,
+              "paged_prefill_attn: at most 2048 pages (32768 positions) per sequence");
+  auto o = torch::empty_like(q);
+  paged_prefill_attn_kernel<<<dim3((Sq + 63) / 64, H, B), dim3(256), 0, cur_stream()>>>(
+      bf16_ptr(q), bf16_ptr(kcache), bf16_ptr(vcache), bf16_mut(o),
+      block_table.data_ptr<int>(), ctx_lens.data_ptr<int>(), q_lens.data_ptr<int>(),
+      Sq, H, Hk, (int)block_table.size(1), (float)scale);
+  HIP_CHECK_KERNEL();
+  return o;
+}
+
 // ---------------- Logit post-processing ----------------
 torch::Tensor argmax_rows(torch::Tensor logits) {
   check_bf16(logits, "logits");
@@ -1082,6 +1122,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_v5_packed", &attn_fwd_v5_packed,
         "attn_fwd_v5 skipping shared-prefix query rows; packed O^T [H*D, Tp] out");
   m.def("paged_decode_attn", &paged_decode_attn, "paged decode attention");
+  m.def("paged_prefill_attn", &paged_prefill_attn,
+        "prefill attention over the paged cache, queries at an offset");
   m.def("argmax_rows", &argmax_rows, "row argmax over bf16 logits");
   m.def("target_logprob", &target_logprob, "fused log_softmax gather");
 }

@@ -125,6 +125,24 @@ def paged_decode_attn_ref(q, kcache, vcache, block_table, ctx_lens, scale):
     return out
 
 
+def paged_prefill_attn_ref(q, kcache, vcache, block_table, ctx_lens, q_lens, scale):
+    """q: [B,Sq,H,D], the q_lens[b] new tokens of sequence b, whose K/V are
+    already in the caches [P, 16, Hk, D]; ctx_lens[b] counts them.  Row i sits
+    at position ctx - q_len + i and sees keys 0 .. that position: built row
+    by row from paged_decode_attn_ref with ctx = hist + i + 1.  Rows
+    i >= q_lens[b] are never read and come back zero."""
+    B, Sq = q.shape[:2]
+    out = torch.zeros_like(q)
+    for b in range(B):
+        ctx, n = int(ctx_lens[b]), int(q_lens[b])
+        assert 1 <= n <= min(Sq, ctx), (n, Sq, ctx)
+        hist = ctx - n
+        rows = torch.arange(hist + 1, ctx + 1, dtype=torch.int32, device=q.device)
+        out[b, :n] = paged_decode_attn_ref(
+            q[b, :n], kcache, vcache, block_table[b:b + 1].expand(n, -1), rows, scale)
+    return out
+
+
 def argmax_rows_ref(logits: torch.Tensor) -> torch.Tensor:
     """Lowest index of the row maximum; NaN entries are ignored (as in the
     kernel, where NaN never wins a comparison), an all-NaN row gives 0."""

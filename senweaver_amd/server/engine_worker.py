@@ -30,7 +30,9 @@ def main() -> int:
 
     model_name = os.environ.get("SENWEAVER_MODEL", "tiny-debug" if not torch.cuda.is_available() else "llama-3-8b")
     max_seq = int(os.environ.get("SENWEAVER_MAX_SEQ", "2048" if torch.cuda.is_available() else "256"))
-    backend = LlamaBackend(get_config(model_name), max_seq=max_seq)
+    # prefix_cache=None: the constructor reads SENWEAVER_PREFIX_CACHE
+    backend = LlamaBackend(get_config(model_name), max_seq=max_seq,
+                           prefix_cache=None)
     service = LLMMessageService(backend)
     out_lock = threading.Lock()
     request_map = {}  # client requestId -> service request id

@@ -218,6 +218,10 @@ def main(argv=None) -> int:
     ap.add_argument("--daemon", default=None, metavar="SOCKET",
                     help="front the native daemon at SOCKET instead of "
                          "loading a model in-process")
+    ap.add_argument("--prefix-cache", action="store_true", default=None,
+                    help="keep the KV cache between generate calls and "
+                         "prefill only past the common prefix (default: "
+                         "env SENWEAVER_PREFIX_CACHE=1)")
     args = ap.parse_args(argv)
 
     import uvicorn
@@ -232,7 +236,8 @@ def main(argv=None) -> int:
 
         model = args.model or ("llama-3-8b" if torch.cuda.is_available()
                                else "tiny-debug")
-        backend = LlamaBackend(model, max_seq=args.max_seq)
+        backend = LlamaBackend(model, max_seq=args.max_seq,
+                               prefix_cache=args.prefix_cache)
     app = create_app(LLMMessageService(backend))
     uvicorn.run(app, host=args.host, port=args.port, log_level="warning")
     return 0
