@@ -102,14 +102,54 @@ void check_bf16(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// Operand checks shared by every dense bf16 GEMM binding (C = A @ B^T).
+// The kernels index both operands from M, N and K alone, so a B of another K,
+// of another rank or on another device must be refused here.
+struct GemmDims { int M, N, K; };
+
+GemmDims check_gemm_operands(const torch::Tensor& a, const torch::Tensor& b,
+                             const char* op) {
+  check_bf16(a, "a");
+  check_bf16(b, "b");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2, op, ": a must be [M, K] and b [N, K]; got ",
+              a.dim(), "-d and ", b.dim(), "-d");
+  TORCH_CHECK(a.device() == b.device(), op, ": a and b must be on one device");
+  TORCH_CHECK(b.size(1) == a.size(1), op, ": K mismatch: a has K=", a.size(1),
+              ", b has K=", b.size(1));
+  return {(int)a.size(0), (int)b.size(0), (int)a.size(1)};
+}
+
+// The 256 x 256-tile bindings: whole tiles only, K a positive multiple of
+// kmult (128 for the counted-vmcnt pipelines, whose prologues need two
+// 64-wide K-tiles; 64 for the full-drain double-buffer kernels).
+GemmDims check_gemm_256(const torch::Tensor& a, const torch::Tensor& b,
+                        const char* op, int kmult) {
+  const GemmDims d = check_gemm_operands(a, b, op);
+  TORCH_CHECK(d.M % 256 == 0 && d.N % 256 == 0 && d.K >= kmult && d.K % kmult == 0,
+              op, " needs M, N % 256 == 0 and K a positive multiple of ", kmult,
+              "; got ", d.M, "x", d.N, "x", d.K);
+  return d;
+}
+
+// rmsnorm / fused_add_rmsnorm: the kernel reads hidden / 8 16-byte vectors
+// of every row of x and of w.  Returns hidden.
+int check_norm_operands(const torch::Tensor& x, const torch::Tensor& w, const char* op) {
+  check_bf16(x, "x");
+  check_bf16(w, "w");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, op, ": x must be [..., hidden]");
+  const int hidden = x.size(-1);
+  TORCH_CHECK(hidden % 8 == 0, op, ": hidden % 8 != 0; got ", hidden);
+  TORCH_CHECK(w.numel() == hidden, op, ": w has ", w.numel(), " elements, hidden is ",
+              hidden);
+  TORCH_CHECK(w.device() == x.device(), op, ": x and w must be on one device");
+  return hidden;
+}
+
 }  // namespace
 
 // ---------------- RMSNorm ----------------
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps) {
-  check_bf16(x, "x");
-  check_bf16(w, "w");
-  const int hidden = x.size(-1);
-  TORCH_CHECK(hidden % 8 == 0, "hidden % 8 != 0");
+  const int hidden = check_norm_operands(x, w, "rmsnorm");
   const long long rows = x.numel() / hidden;
   auto y = torch::empty_like(x);
   rmsnorm_fwd_kernel<<<dim3((unsigned)rows), dim3(256), 0, cur_stream()>>>(
@@ -121,10 +161,10 @@ torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps) {
 // y = rmsnorm(x + residual); residual <- x + residual (in place)
 torch::Tensor fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
                                 torch::Tensor w, double eps) {
-  check_bf16(x, "x");
+  const int hidden = check_norm_operands(x, w, "fused_add_rmsnorm");
   check_bf16(residual, "residual");
-  check_bf16(w, "w");
-  const int hidden = x.size(-1);
+  TORCH_CHECK(residual.sizes() == x.sizes() && residual.device() == x.device(),
+              "fused_add_rmsnorm: residual must have x's shape and device");
   const long long rows = x.numel() / hidden;
   auto y = torch::empty_like(x);
   rmsnorm_fwd_kernel<<<dim3((unsigned)rows), dim3(256), 0, cur_stream()>>>(
@@ -140,10 +180,18 @@ void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor cos_sin,
   check_bf16(k, "k");
   TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_contiguous());
   TORCH_CHECK(positions.scalar_type() == torch::kInt32 && positions.is_contiguous());
+  TORCH_CHECK(k.device() == q.device() && cos_sin.device() == q.device() &&
+              positions.device() == q.device(),
+              "rope_inplace: q, k, cos_sin and positions must be on one GPU");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && cos_sin.dim() == 2,
+              "rope_inplace: q [T,Hq,D], k [T,Hk,D], cos_sin [max_pos,D]");
   const int T = q.size(0);
   const int Hq = q.size(1), Hk = k.size(1), D = q.size(2);
   TORCH_CHECK(k.size(0) == T && k.size(2) == D);
-  TORCH_CHECK(cos_sin.size(1) == D);
+  TORCH_CHECK(cos_sin.size(1) == D && D % 2 == 0);
+  // the kernel reads positions[t] for every one of the T grid rows
+  TORCH_CHECK(positions.numel() == T, "rope_inplace: ", positions.numel(),
+              " positions for ", T, " tokens");
   rope_fwd_kernel<<<dim3(T, Hq + Hk), dim3(64), 0, cur_stream()>>>(
       bf16_mut(q), bf16_mut(k), cos_sin.data_ptr<float>(),
       positions.data_ptr<int>(), Hq, Hk, D);
@@ -272,10 +320,8 @@ torch::Tensor add_bf16(torch::Tensor a, torch::Tensor b) {
 
 // ---------------- GEMM: C[M,N] = A[M,K] @ B[N,K]^T ----------------
 torch::Tensor gemm_bt(torch::Tensor A, torch::Tensor B) {
-  check_bf16(A, "A");
-  check_bf16(B, "B");
-  const int M = A.size(0), K = A.size(1), N = B.size(0);
-  TORCH_CHECK(B.size(1) == K, "K mismatch");
+  const GemmDims d = check_gemm_operands(A, B, "gemm_bt");
+  const int M = d.M, K = d.K, N = d.N;
   auto C = torch::empty({M, N}, A.options());
   if (M <= 16) {
     TORCH_CHECK(N % 4 == 0 && K >= 512 && K % 512 == 0,
@@ -312,7 +358,8 @@ torch::Tensor gemm_bt(torch::Tensor A, torch::Tensor B) {
     HIP_CHECK_KERNEL();
     return C;
   }
-  TORCH_CHECK(K % 64 == 0, "gemm_bt needs K % 64 == 0; got K=", K);
+  TORCH_CHECK(K >= 64 && K % 64 == 0,
+              "gemm_bt needs K a positive multiple of 64; got K=", K);
   // 256-tile kernels run 1 block/CU (128 KiB LDS): they need >=~160 blocks
   // to fill 256 CUs; below that the 2-block/CU 128-tile kernel wins.
   if (M % 256 == 0 && N % 256 == 0 && (M / 256) * (N / 256) >= 160) {
@@ -912,9 +959,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_bf16", &add_bf16, "a + b (bf16)");
   m.def("gemm_bt", &gemm_bt, "C = A @ B^T (bf16 MFMA)");
   m.def("gemm_bt_8ph", [](torch::Tensor a, torch::Tensor b) {
-    check_bf16(a, "a"); check_bf16(b, "b");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0);
+    const GemmDims d = check_gemm_256(a, b, "gemm_bt_8ph", 128);
+    const int M = d.M, K = d.K, N = d.N;
     auto C = torch::empty({M, N}, a.options());
     gemm_bt_bf16_8ph_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
         bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);
@@ -922,9 +968,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return C;
   }, "256-tile 8-phase deep-pipelined GEMM (counted vmcnt)");
   m.def("gemm_bt_8ph_v", [](torch::Tensor a, torch::Tensor b, long var) {
-    check_bf16(a, "a"); check_bf16(b, "b");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0);
+    const GemmDims d = check_gemm_256(a, b, "gemm_bt_8ph_v", 128);
+    const int M = d.M, K = d.K, N = d.N;
     auto C = torch::empty({M, N}, a.options());
     const dim3 g((M / 256) * (N / 256)), blk(512);
     switch (var) {
@@ -972,8 +1017,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
       case 24: gemm_bt_bf16_asm7_kernel<<<g, dim3(512), 0, cur_stream()>>>(
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      default: gemm_bt_bf16_8ph_kernel<<<g, blk, 0, cur_stream()>>>(
+      case 0: gemm_bt_bf16_8ph_kernel<<<g, blk, 0, cur_stream()>>>(
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
+      default:
+        TORCH_CHECK(false, "gemm_bt_8ph_v: unknown variant ", var,
+                    " (known: 0-9, 11-14, 16-24)");
     }
     HIP_CHECK_KERNEL();
     return C;
@@ -1068,9 +1116,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return C;
   }, "fused silu(g)*u + streaming GEMV (decode down-proj, M=1)");
   m.def("gemm_bt_256x32", [](torch::Tensor a, torch::Tensor b) {
-    check_bf16(a, "a"); check_bf16(b, "b");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0);
+    const GemmDims d = check_gemm_256(a, b, "gemm_bt_256x32", 64);
+    const int M = d.M, K = d.K, N = d.N;
     auto C = torch::empty({M, N}, a.options());
     gemm_bt_bf16_256x32_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
         bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);
@@ -1078,9 +1125,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return C;
   }, "256-tile GEMM on 32x32x16 MFMA (A/B experiment)");
   m.def("gemm_bt_256sg", [](torch::Tensor a, torch::Tensor b) {
-    check_bf16(a, "a"); check_bf16(b, "b");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0);
+    const GemmDims d = check_gemm_256(a, b, "gemm_bt_256sg", 64);
+    const int M = d.M, K = d.K, N = d.N;
     auto C = torch::empty({M, N}, a.options());
     gemm_bt_bf16_256sg_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
         bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);

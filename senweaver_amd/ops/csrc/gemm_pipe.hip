@@ -37,6 +37,34 @@
 //
 // Constraints: M % 256 == 0 (host pads), N % 256 == 0, K % 128 == 0
 // (even K-tile count keeps the double-buffer flip compile-time).
+//
+// Prologues and the smallest K.  Every body in this file (and the asm kernels
+// generated into gemm_asm.hip, which copy the gemm2ph_body prologue) issues
+// tile 0 in full and part of tile 1, then waits with a COUNTED vmcnt sized
+// for exactly the tile-1 loads it issued.  Each issue is skipped when its
+// tile does not exist (TGT < ntiles), so with ONE K-tile the tile-1 loads
+// would be missing from the count and the wait would let tile-0 loads still
+// be in flight at the first barrier.  No body handles that case; all of them
+// need ntiles >= 2, and the bindings guarantee it: gemm_bt_8ph,
+// gemm_bt_8ph_v and the 256-tile branch of gemm_bt that reaches v14 / asm4 /
+// asm7 accept only K >= 128 with K % 128 == 0, and a K-tile here is PBK = 64
+// (32 for v16 / v17), so K = 128 is two tiles (four for v16 / v17), never one.
+// What has landed at the first barrier at that smallest K, per body:
+//   gemm8ph_body (v0-v3):      8 loads of tile 0, then 6 of tile 1 (slots
+//                              0-2), vmcnt(6): all of tile 0.
+//   gemm8ph_full_body (v4/5/7): B(0), A(0), B(1) 4 loads each, vmcnt(4):
+//                              B(0) and A(0).  MODE 3 (v6): half of B(1),
+//                              2 loads, vmcnt(2): the same.
+//   gemm2ph_body (v8/9/11/12): B(0), A(0), B(1) 4 loads each, vmcnt(4):
+//                              B(0) and A(0).  asm/asm2-asm7 (v18-v24): same.
+//   gemm2ph_wide_body (v13/14): 2 loads per unit at 1024 threads, vmcnt(2):
+//                              B(0) and A(0).
+//   v16: 2 loads per unit, vmcnt(2); v17: A 2 loads, B 1, vmcnt(1): B(0), A(0).
+// In the loop the last two tiles wait vmcnt(0) (t >= ntiles - 2), so at
+// ntiles == 2 the prologue runs straight into the drain.  K = 128 .. 640 is
+// pinned bit for bit by tests/test_gemm_edges_gpu.py for v14, asm4 and asm7.
+// gemm_bt_bf16_kernel and gemm_bt_bf16_256_kernel (gemm.hip) drain with
+// __syncthreads per tile and take a single tile (K = 64).
 
 #include "common.h"
 

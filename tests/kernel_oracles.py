@@ -1,9 +1,11 @@
 """fp64 oracles, input generators and error bounds for the decode kernels,
 the prefill attention kernels, the tiled quantized GEMMs (fp8 / mxfp8), the
-grouped GEMM, the quantizers and moe_combine.
+grouped GEMM, the quantizers and moe_combine, the dense bf16 GEMM kernels
+and the elementwise kernels.
 
 Helper module for test_kernel_oracles_cpu.py, test_decode_edges_gpu.py,
-test_prefill_edges_gpu.py and test_quant_gemm_edges_gpu.py (no tests live
+test_prefill_edges_gpu.py, test_quant_gemm_edges_gpu.py,
+test_gemm_edges_gpu.py and test_elemwise_edges_gpu.py (no tests live
 here).  Every oracle takes the
 SAME bf16 / uint8 tensors the kernel gets, upcasts with ``.double()`` and computes in plain torch on the
 CPU, so the only error in an oracle is fp64 rounding (~1e-16 relative).
@@ -1552,3 +1554,296 @@ def check_moe_combine(fn, T, k, H, dev, gen):
         else:
             assert tuple(got.shape) == (T, H), what
             assert_within(got, ref, U_BF16_OUT * ref.abs() + k * U_FP32 * absum, what)
+
+
+# --------------------------------------------------------------------------
+# Dense bf16 GEMM.  ``fn(a [M,K] bf16, b [N,K] bf16) -> C = a @ b^T [M,N] bf16``
+# --------------------------------------------------------------------------
+GEMM_KFACTOR = 1   # check_gemm_random: the bound the grouped bf16 GEMM meets
+
+
+def gemm_probe_columns(K: int) -> list:
+    """Column 0, K - 1 and both sides of every 8 / 16 / 32 / 64 / 128
+    boundary: the 16-byte LDS chunk, the pair of chunks one swizzle step
+    moves, the k-half of an MFMA step (the ^64-byte read offset), the
+    64-element K-tile and the pair of tiles of one double-buffer round."""
+    cols = {0, K - 1}
+    for step in (8, 16, 32, 64, 128):
+        for b in range(step, K, step):
+            cols.update((b - 1, b))
+    return sorted(c for c in cols if 0 <= c < K)
+
+
+def gemm_onehot_operand(gen, rows: int, K: int, call: int = 0):
+    """[rows, K] bf16 with one non-zero element per row: +-2^e, e in
+    [-3, 3], at probe column cols[(call * rows + r) % len(cols)].
+    Returns (x, col [rows] int64, val [rows] fp64)."""
+    cols = gemm_probe_columns(K)
+    col = torch.tensor([cols[(call * rows + r) % len(cols)] for r in range(rows)])
+    val = _pow2(torch.randint(-3, 4, (rows,), generator=gen))
+    val = val * (torch.randint(0, 2, (rows,), generator=gen).double() * 2 - 1)
+    x = torch.zeros(rows, K, dtype=BF16)
+    x[torch.arange(rows), col] = val.to(BF16)
+    return x, col, val
+
+
+def gemm_onehot_ncalls(rows: int, K: int) -> int:
+    """Calls needed for ``rows`` rows to visit every probe column."""
+    return -(-len(gemm_probe_columns(K)) // rows)
+
+
+def check_gemm_onehot(fn, M, N, K, dev, gen, sides=("a", "b")):
+    """One-hot in K on A, then on B (the two operands go through different
+    LDS buffers), the other operand random: every C[m, n] is +-2^e times one
+    element of the random operand, a bf16 value, and must come out bit for
+    bit (the zero products and the fp32 sums of zeros are exact).  Pins the
+    chunk swizzle, the k-half offset, the tile <-> LDS slot map and the last
+    tile; the random sign and exponent of every row also tell rows apart."""
+    for side in sides:
+        rows, orows = (M, N) if side == "a" else (N, M)
+        other = rand_bf16(gen, orows, K)
+        od = other.to(dev)
+        for call in range(gemm_onehot_ncalls(rows, K)):
+            x, col, val = gemm_onehot_operand(gen, rows, K, call)
+            picked = other.double()[:, col]                       # [orows, rows]
+            if side == "a":
+                ref = picked.t() * val.unsqueeze(1)
+                got = fn(x.to(dev), od)
+            else:
+                ref = picked * val.unsqueeze(0)
+                got = fn(od, x.to(dev))
+            exp = exact_bf16(ref)
+            assert torch.equal(exp.double(), ref), "generator: expectation is not a bf16 value"
+            assert_bits_equal(got, exp, f"gemm one-hot in {side.upper()} M={M} N={N} K={K} call {call}")
+
+
+def gemm_int_operands(gen, M, N, K):
+    """A in [-2, 2], B in [-4, 4], every row random."""
+    return int_x(gen, M, K), torch.randint(-4, 5, (N, K), generator=gen).to(BF16)
+
+
+def check_gemm_int(fn, M, N, K, dev, gen):
+    """Small integers over all of K: |any partial sum| <= 8 K < 2^24, so the
+    fp32 sums are exact in any order and C == bf16_rne(exact sum) bit for
+    bit.  The expectation is an fp32 CPU matmul, exact for the same reason.
+    Catches a dropped or doubled K-tile, a buffer-parity slip, a swapped or
+    duplicated output tile and a wrong C store offset."""
+    a, b = gemm_int_operands(gen, M, N, K)
+    assert 8 * K < 2 ** 24
+    exp = exact_bf16((a.float() @ b.float().t()).double())
+    got = fn(a.to(dev), b.to(dev))
+    assert_bits_equal(got, exp, f"gemm integer M={M} N={N} K={K}")
+
+
+def check_gemm_random(fn, M, N, K, dev, gen, kfactor=None):
+    """randn operands against the fp64 product, elementwise within
+    gemv_bound(ref, |A|.|B|^T, K, GEMM_KFACTOR) = 2^-8 |ref| + K 2^-24
+    |A|.|B|^T: bf16 output rounding plus worst-case fp32 summation in any
+    order (bf16 x bf16 products are exact in fp32).  Returns (and prints)
+    the worst err / bound."""
+    a, b = rand_bf16(gen, M, K), rand_bf16(gen, N, K)
+    ref = a.double() @ b.double().t()
+    absdot = a.double().abs() @ b.double().abs().t()
+    bound = gemv_bound(ref, absdot, K, GEMM_KFACTOR if kfactor is None else kfactor)
+    got = fn(a.to(dev), b.to(dev))
+    what = f"gemm random M={M} N={N} K={K}"
+    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)}"
+    ratio = float(((got.detach().cpu().double() - ref).abs() / bound).max())
+    print(f"{what}: max err / bound = {ratio:.3f}")
+    assert_within(got, ref, bound, what)
+    return ratio
+
+
+def check_gemm_all(fn, M, N, K, dev, gen):
+    check_gemm_onehot(fn, M, N, K, dev, gen)
+    check_gemm_int(fn, M, N, K, dev, gen)
+    return check_gemm_random(fn, M, N, K, dev, gen)
+
+
+# --------------------------------------------------------------------------
+# Elementwise ops: add_bf16, rmsnorm, fused_add_rmsnorm, swiglu(_padded),
+# rope_inplace
+# --------------------------------------------------------------------------
+def bf16_rne64(v64: torch.Tensor) -> torch.Tensor:
+    """Round-to-nearest-even of fp64 values to bf16 in ONE rounding (normal
+    range; written out so the expectation never passes through fp32)."""
+    a = v64.abs()
+    nz = a > 0
+    assert float(a[nz].min()) >= 2.0 ** -126 if bool(nz.any()) else True
+    _, ex = torch.frexp(a)                       # a = m 2^ex, m in [0.5, 1)
+    q = _pow2(ex.long() - 8)                     # bf16 spacing: 8 significand bits
+    r = torch.where(nz, torch.round(a / q) * q, torch.zeros_like(a))   # half to even
+    return exact_bf16(torch.where(v64 < 0, -r, r))
+
+
+ADD_PLANTED = [(1.0, 2.0 ** -8, 1.0),                      # tie -> even (down)
+               (1.0 + 2.0 ** -7, 2.0 ** -8, 1.0 + 2.0 ** -6),   # tie -> even (up)
+               (256.0, 1.0, 256.0), (258.0, 1.0, 260.0),   # ties at another binade
+               (-1.0, -(2.0 ** -8), -1.0),
+               (1.5, -1.5, 0.0),                           # exact cancellation: +0
+               (1.0, 2.0 ** -20, 1.0),                     # far apart: the large one
+               (3.0, 2.0 ** -7 + 2.0 ** -8, 3.0 + 2.0 ** -6)]   # just past a tie -> up
+
+
+def add_inputs(gen, n: int):
+    """Two bf16 vectors of n elements: randn times 2^[-6, 6] per element (so
+    the exponents of a pair differ), the planted pairs of ADD_PLANTED first."""
+    def draw():
+        e = torch.randint(-6, 7, (n,), generator=gen)
+        return (torch.randn(n, generator=gen, dtype=torch.float64) * _pow2(e)).to(BF16)
+
+    a, b = draw(), draw()
+    for i, (x, y, s) in enumerate(ADD_PLANTED[:n]):
+        a[i], b[i] = x, y
+        assert float(a[i]) == x and float(b[i]) == y, "generator: not bf16 values"
+        assert float(bf16_rne64(torch.tensor([x + y], dtype=torch.float64))) == s
+    return a, b
+
+
+def check_add_bf16(fn, n, dev, gen):
+    """fn(a, b) -> a + b: bit-equal to RNE of the exact (fp64) sum.  The fp32
+    sum the kernel rounds from is exact or, where the exponents are more than
+    16 apart, far from any bf16 midpoint, so one rounding is the contract."""
+    a, b = add_inputs(gen, n)
+    got = fn(a.to(dev), b.to(dev))
+    assert_bits_equal(got, bf16_rne64(a.double() + b.double()), f"add_bf16 n={n}")
+
+
+def rmsnorm_ref64(x, w, eps) -> torch.Tensor:
+    xd = x.cpu().double()
+    return xd * torch.rsqrt((xd * xd).mean(dim=-1, keepdim=True) + eps) * w.cpu().double()
+
+
+def rmsnorm_bound(ref64: torch.Tensor, hidden: int) -> torch.Tensor:
+    """(2^-8 + (hidden / 2 + 16) 2^-24) |ref|.  2^-8 |ref| is the bf16 output
+    rounding.  The fp32 value it rounds from: hidden squares (one rounding
+    each) summed in any order are off by at most hidden 2^-24 relative (all
+    terms are non-negative), the reciprocal square root halves that; the
+    division by hidden, the + eps, rsqrt and the two products are an ulp or
+    two each (16 covers them and the (1 + 2^-8) cross term)."""
+    return (U_BF16_OUT + (hidden / 2 + 16) * U_FP32) * ref64.abs()
+
+
+def rmsnorm_pow2_case(gen, rows: int, hidden: int):
+    """Rows of +-2^j (j per row), weights +-2^k (k per column), eps = 1e-12:
+    the sum of squares hidden 4^j is exact in fp32, the mean is exactly 4^j
+    (a correctly rounded division), eps < 2^-39 cannot move it (4^j >= 2^-8),
+    so the scale is 2^-j and y = sign(x) w exactly.  Returns (x, w, eps, y)."""
+    j = torch.randint(-4, 5, (rows, 1), generator=gen)
+    sx = torch.randint(0, 2, (rows, hidden), generator=gen).double() * 2 - 1
+    k = torch.randint(-3, 4, (hidden,), generator=gen)
+    sw = torch.randint(0, 2, (hidden,), generator=gen).double() * 2 - 1
+    x, w = (sx * _pow2(j)).to(BF16), (sw * _pow2(k)).to(BF16)
+    eps = 1e-12
+    y = exact_bf16(sx * w.double())
+    ref = rmsnorm_ref64(x, w, eps)
+    assert float(((ref - y.double()).abs() / ref.abs()).max()) < 2.0 ** -30, "generator"
+    return x, w, eps, y
+
+
+def check_rmsnorm(fn, rows, hidden, dev, gen, eps=1e-5):
+    """fn(x [rows, hidden], w [hidden], eps) -> y.  Bit-exact on the
+    power-of-two case; within rmsnorm_bound of the fp64 reference on randn
+    rows of different scales with randn weights."""
+    x, w, e0, y = rmsnorm_pow2_case(gen, rows, hidden)
+    got = fn(x.to(dev), w.to(dev), e0)
+    assert_bits_equal(got, y, f"rmsnorm power-of-two rows={rows} hidden={hidden}")
+    scale = _pow2(torch.randint(-3, 4, (rows, 1), generator=gen))
+    x = (torch.randn(rows, hidden, generator=gen, dtype=torch.float64) * scale).to(BF16)
+    w = rand_bf16(gen, hidden)
+    ref = rmsnorm_ref64(x, w, eps)
+    got = fn(x.to(dev), w.to(dev), eps)
+    assert_within(got, ref, rmsnorm_bound(ref, hidden),
+                  f"rmsnorm random rows={rows} hidden={hidden}")
+
+
+def check_fused_add_rmsnorm(fn, rows, hidden, dev, gen, eps=1e-5):
+    """fn(x, res, w, eps) -> (y, res_out).  res_out is bit-equal to RNE(x +
+    res); y is the norm of that ROUNDED sum (what the kernel re-reads), bit
+    for bit on the power-of-two case (x = res = +-2^(j-1)) and within
+    rmsnorm_bound on the add_inputs data."""
+    x, w, e0, y = rmsnorm_pow2_case(gen, rows, hidden)
+    half = (x.double() / 2).to(BF16)
+    got, r = fn(half.to(dev), half.clone().to(dev), w.to(dev), e0)
+    what = f"fused_add_rmsnorm rows={rows} hidden={hidden}"
+    assert_bits_equal(r, x, what + " power-of-two residual")
+    assert_bits_equal(got, y, what + " power-of-two y")
+    a, b = add_inputs(gen, rows * hidden)
+    a, b = a.view(rows, hidden), b.view(rows, hidden)
+    w = rand_bf16(gen, hidden)
+    got, r = fn(a.to(dev), b.clone().to(dev), w.to(dev), eps)
+    r_exp = bf16_rne64(a.double() + b.double())
+    assert_bits_equal(r, r_exp, what + " residual")
+    ref = rmsnorm_ref64(r_exp, w, eps)
+    assert_within(got, ref, rmsnorm_bound(ref, hidden), what + " y")
+
+
+SWIGLU_EDGE_G = [0.0, 32.0, -32.0, 8.0, -8.0, 0.5, -0.5, 2.0 ** -20]
+
+
+def swiglu_inputs(gen, rows: int, inter: int) -> torch.Tensor:
+    """gateup [rows, 2 inter]: 2 randn, with SWIGLU_EDGE_G planted in the
+    first and in the last 8-vector of row 0's gate (up = 1.5 there)."""
+    gu = (torch.randn(rows, 2 * inter, generator=gen) * 2).to(BF16)
+    if rows:
+        edge = torch.tensor(SWIGLU_EDGE_G, dtype=BF16)
+        for c0 in (0, inter - 8):
+            gu[0, c0:c0 + 8] = edge
+            gu[0, inter + c0:inter + c0 + 8] = 1.5
+    return gu
+
+
+def swiglu_bound(gateup: torch.Tensor) -> torch.Tensor:
+    """(2^-8 + (2 |g| + 8) 2^-24) |ref| around swiglu_ref64.  The kernel
+    takes exp(-g) as exp2(-g log2 e) in fp32: the rounded constant and the
+    rounded product each move the exponent by |g log2 e| 2^-24, the result by
+    |g| 2^-24 relative, and 1 + exp(-g) no more than that; v_exp_f32, the
+    sum, the division and the product with u are an ulp or two each."""
+    g = gateup.cpu().double()[..., :gateup.shape[-1] // 2]
+    return (U_BF16_OUT + (2 * g.abs() + 8) * U_FP32) * swiglu_ref64(gateup).abs()
+
+
+def check_swiglu(fn, fn_padded, rows, inter, dev, gen):
+    """fn(gateup) -> [rows, inter] within swiglu_bound; fn_padded(gateup,
+    out_rows) for out_rows = rows, rows + 1 and rows + 3: the first rows
+    bit-equal to fn's, the pad rows +0.  silu(32) = 32 and silu(0) = 0 come
+    out exactly (1 + exp(-32) == 1 in fp32)."""
+    gu = swiglu_inputs(gen, rows, inter)
+    gd = gu.to(dev)
+    what = f"swiglu rows={rows} inter={inter}"
+    y = None
+    if rows:
+        y = fn(gd)
+        assert tuple(y.shape) == (rows, inter), what
+        assert_within(y, swiglu_ref64(gu), swiglu_bound(gu), what)
+        yc = y.detach().cpu().float()
+        for c0 in (0, inter - 8):
+            assert float(yc[0, c0]) == 0.0 and float(yc[0, c0 + 1]) == 48.0, what + " edges"
+    for out_rows in (rows, rows + 1, rows + 3):
+        yp = fn_padded(gd, out_rows)
+        assert tuple(yp.shape) == (out_rows, inter), f"{what} out_rows={out_rows}"
+        if rows:
+            assert_bits_equal(yp[:rows].contiguous(), y, f"{what} out_rows={out_rows} head")
+        pad = bits(yp[rows:].contiguous())
+        assert bool((pad == 0).all()), f"{what} out_rows={out_rows}: pad rows are not +0"
+
+
+def check_rope_inplace(fn, Hq, Hk, D, dev, gen, rope_tables, max_pos=300):
+    """fn(q [T,Hq,D], k [T,Hk,D], cos_sin, positions) rotates in place.
+    Positions repeat and include 0 (cos = 1, sin = 0: bit-equal to the input)
+    and max_pos - 1; every element within the rope_ref64 bound."""
+    pos = torch.tensor([0, 5, 5, max_pos - 1, 0, 17, 5], dtype=torch.int32)
+    T = pos.numel()
+    q0, k0 = rand_bf16(gen, T, Hq, D), rand_bf16(gen, T, Hk, D)
+    cs = rope_tables(max_pos, D, 500000.0)
+    q, k = q0.clone().to(dev), k0.clone().to(dev)
+    fn(q, k, cs.to(dev), pos.to(dev))
+    what = f"rope_inplace Hq={Hq} Hk={Hk} D={D}"
+    for got, x0, nm in ((q, q0, "q"), (k, k0, "k")):
+        r64, bnd = rope_ref64(x0, cs, pos)
+        assert_within(got, r64, bnd, f"{what} {nm}")
+        z = (pos == 0).nonzero().flatten()
+        assert_bits_equal(got.cpu()[z].contiguous(), x0[z].contiguous(),
+                          f"{what} {nm} at position 0")
+        same = (pos == 5).nonzero().flatten()      # the table row is shared, not the data
+        assert not torch.equal(got.cpu()[same[0]], got.cpu()[same[1]])

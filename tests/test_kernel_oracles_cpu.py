@@ -1,5 +1,6 @@
-"""CPU checks of the decode-kernel, prefill-attention and quantized GEMM /
-quantizer / MoE oracles (tests/kernel_oracles.py).
+"""CPU checks of the decode-kernel, prefill-attention, quantized GEMM /
+quantizer / MoE, dense bf16 GEMM and elementwise oracles
+(tests/kernel_oracles.py).
 
 Three things are established without a GPU:
 1. each fp64 oracle agrees with the existing fp32 reference in
@@ -1068,3 +1069,249 @@ def test_combine_using_a_pad_row_rejected(gen):
         return ref.moe_combine_ref(down, pos, w)
 
     _rejected(ko.check_moe_combine, bad, 7, 2, 264, CPU, gen)
+
+
+# ---------------- dense bf16 GEMM ----------------
+GEMM_CPU_SHAPES = [(128, 128, 64), (256, 256, 256), (384, 640, 320), (17, 256, 128)]
+GM = (256, 256, 256)      # mutants: square, 2 x 2 output tiles of 128, 4 K-tiles of 64
+GEMM_CHECKS = {"onehot_a": lambda fn, *a: ko.check_gemm_onehot(fn, *a, sides=("a",)),
+               "onehot_b": lambda fn, *a: ko.check_gemm_onehot(fn, *a, sides=("b",)),
+               "int": ko.check_gemm_int,
+               "random": ko.check_gemm_random}
+
+
+@pytest.mark.parametrize("K", [64, 128, 192, 256, 320, 384, 512, 640])
+def test_gemm_probe_columns_cover_boundaries(K):
+    cols = ko.gemm_probe_columns(K)
+    assert cols[0] == 0 and cols[-1] == K - 1 and cols == sorted(set(cols))
+    for step in (8, 16, 32, 64, 128):
+        for b in range(step, K, step):
+            assert b - 1 in cols and b in cols
+    # every 8-element chunk of every K-tile holds a probe
+    assert {c // 8 for c in cols} == set(range(K // 8))
+    # the rows of the smallest tile visit all of them in the calls made
+    for rows in (17, 128, 256):
+        seen = set()
+        for call in range(ko.gemm_onehot_ncalls(rows, K)):
+            seen |= set(ko.gemm_onehot_operand(torch.Generator().manual_seed(1), rows, K,
+                                               call)[1].tolist())
+        assert seen == set(cols)
+
+
+def test_gemm_onehot_operand_is_onehot_pow2(gen):
+    x, col, val = ko.gemm_onehot_operand(gen, 300, 640)
+    assert bool(((x != 0).sum(dim=1) == 1).all())
+    assert torch.equal(x[torch.arange(300), col].double(), val)
+    assert bool(ko.is_pow2(val.abs()).all()) and bool((val < 0).any()) and bool((val > 0).any())
+    assert float(val.abs().min()) >= 2.0 ** -3 and float(val.abs().max()) <= 2.0 ** 3
+
+
+def test_gemm_int_sums_stay_exact_in_fp32(gen):
+    """At the largest K and the largest shape of the GPU file: the fp32 CPU
+    matmul that serves as the expectation equals the fp64 one."""
+    a, b = ko.gemm_int_operands(gen, 256, 384, 640)
+    assert float(ko.gemv_abs_dot(a, b.double()).max()) < 2 ** 24
+    assert torch.equal((a.float() @ b.float().t()).double(), a.double() @ b.double().t())
+    for t in (a, b):      # every row differs from every other: tiles are distinguishable
+        assert torch.unique(t, dim=0).shape[0] == t.shape[0]
+
+
+@pytest.mark.parametrize("M,N,K", GEMM_CPU_SHAPES)
+def test_gemm_fp32_reference_passes_every_check(gen, M, N, K):
+    """The correct fp32-accumulating operator (and ops.gemm_bt's CPU route,
+    which is the same thing) passes all three checks at kfactor 1."""
+    for fn in (ref.gemm_bt_ref, ops.gemm_bt, ops.gemm_bt_tiled):
+        assert ko.check_gemm_all(fn, M, N, K, CPU, gen) <= 1.0
+
+
+def gemm_mutant(name, operand="a"):
+    """ref.gemm_bt_ref with one property of a tiled kernel switched.  The K
+    mutants act on tile 1 (of 64) of one operand, as a fault in that
+    operand's LDS buffer would; the output mutants on 128 x 128 tiles."""
+    def permute_k(x, idx):
+        return x[:, idx]
+
+    def fn(a, b):
+        K = a.shape[1]
+        k = torch.arange(K)
+        if name in ("drop_k_tile", "swap_chunks", "swap_khalves"):
+            if name == "drop_k_tile":               # the K loop skips a tile
+                keep = ((k < 64) | (k >= 128)).to(a.dtype)
+                mut = lambda x: x * keep
+            elif name == "swap_chunks":             # chunks 2 and 5 of tile 1 exchanged
+                idx = k.clone()
+                idx[80:88], idx[104:112] = k[104:112], k[80:88]
+                mut = lambda x: permute_k(x, idx)
+            else:                                   # the ^64-byte k-half offset inverted
+                idx = k.clone()
+                idx[64:96], idx[96:128] = k[96:128], k[64:96]
+                mut = lambda x: permute_k(x, idx)
+            a, b = (mut(a), b) if operand == "a" else (a, mut(b))
+            return ref.gemm_bt_ref(a, b)
+        if name == "double_k_tile":                 # a buffer-parity slip: tile 1 read twice
+            c = a.float() @ b.float().t() + a[:, 64:128].float() @ b[:, 64:128].float().t()
+            return c.to(a.dtype)
+        c = ref.gemm_bt_ref(a, b)
+        if name == "swap_out_tiles":                # a hole in the workgroup remap
+            c = c.clone()
+            t = c[:128, :128].clone()
+            c[:128, :128] = c[128:256, 128:256]
+            c[128:256, 128:256] = t
+        elif name == "dup_out_tile":                # two workgroups on one tile
+            c = c.clone()
+            c[128:256, :128] = c[:128, :128]
+        elif name == "transposed":
+            c = c.t().contiguous()
+        elif name == "one_ulp":
+            c = c.clone()
+            c[200, 77] = _next_bf16(c[200, 77])
+        else:
+            raise ValueError(name)
+        return c
+    return fn
+
+
+def test_gemm_mutants_are_cut_from_a_passing_operator(gen):
+    for check in GEMM_CHECKS.values():
+        check(ref.gemm_bt_ref, *GM, CPU, gen)
+
+
+@pytest.mark.parametrize("check", ["onehot_a", "onehot_b", "int", "random"])
+@pytest.mark.parametrize("operand", ["a", "b"])
+@pytest.mark.parametrize("name", ["drop_k_tile", "swap_chunks", "swap_khalves"])
+def test_gemm_k_tile_mutants_rejected_by_onehot_int_and_random(gen, name, operand, check):
+    _rejected(GEMM_CHECKS[check], gemm_mutant(name, operand), *GM, CPU, gen)
+
+
+@pytest.mark.parametrize("check", ["onehot_a", "onehot_b", "int", "random"])
+@pytest.mark.parametrize("name", ["double_k_tile", "swap_out_tiles", "dup_out_tile",
+                                  "transposed"])
+def test_gemm_tile_mutants_rejected_by_onehot_int_and_random(gen, name, check):
+    _rejected(GEMM_CHECKS[check], gemm_mutant(name), *GM, CPU, gen)
+
+
+@pytest.mark.parametrize("check", ["onehot_a", "onehot_b", "int"])
+def test_gemm_one_ulp_rejected_by_onehot_and_int(gen, check):
+    """One element off by one bf16 ulp fails both bit-exact checks (the
+    random check allows half an ulp of rounding and cannot see it)."""
+    _rejected(GEMM_CHECKS[check], gemm_mutant("one_ulp"), *GM, CPU, gen)
+
+
+# ---------------- elementwise ops ----------------
+ELEM_HIDDEN = [8, 2040, 2048, 2056]
+
+
+def _cpu_add(a, b):
+    return (a.float() + b.float()).to(torch.bfloat16)
+
+
+def _cpu_fused(x, res, w, eps):
+    y = ops.fused_add_rmsnorm(x, res, w, eps)
+    return y, res
+
+
+def _cpu_swiglu_padded(gu, out_rows):
+    return ops.swiglu(gu, out_rows=out_rows)
+
+
+def test_bf16_rne64_rounds_once_to_nearest_even(gen):
+    v = torch.tensor([1.0 + 2.0 ** -8, 1.0 + 2.0 ** -8 + 2.0 ** -40, 1.0 + 3 * 2.0 ** -8,
+                      -(1.0 + 2.0 ** -8), 255.5, 0.0, 2.0 ** -100 * (1 + 2.0 ** -8)],
+                     dtype=torch.float64)
+    exp = [1.0, 1.0 + 2.0 ** -7, 1.0 + 2.0 ** -6, -1.0, 256.0, 0.0, 2.0 ** -100]
+    assert ko.bf16_rne64(v).double().tolist() == exp
+    # 1 + 2^-8 + 2^-40 through fp32 first would lose the 2^-40 and tie down to 1
+    assert float(v[1].float().to(torch.bfloat16)) == 1.0
+    x = torch.randn(4096, generator=gen, dtype=torch.float64).float().double()
+    assert torch.equal(ko.bf16_rne64(x), x.float().to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("n", [8, 2048, 8 * 256 * 3 + 8])
+def test_cpu_add_passes(gen, n):
+    ko.check_add_bf16(_cpu_add, n, CPU, gen)
+
+
+@pytest.mark.parametrize("hidden", ELEM_HIDDEN)
+@pytest.mark.parametrize("rows", [1, 3])
+def test_cpu_rmsnorm_fallbacks_pass(gen, rows, hidden):
+    ko.check_rmsnorm(ops.rmsnorm, rows, hidden, CPU, gen)
+    ko.check_fused_add_rmsnorm(_cpu_fused, rows, hidden, CPU, gen)
+
+
+@pytest.mark.parametrize("inter", [8, 2040, 2056])
+@pytest.mark.parametrize("rows", [0, 1, 3])
+def test_cpu_swiglu_fallback_passes(gen, rows, inter):
+    ko.check_swiglu(ops.swiglu, _cpu_swiglu_padded, rows, inter, CPU, gen)
+
+
+@pytest.mark.parametrize("Hq,Hk", [(1, 1), (6, 2)])
+@pytest.mark.parametrize("D", [32, 128, 256])
+def test_cpu_rope_inplace_fallback_passes(gen, D, Hq, Hk):
+    ko.check_rope_inplace(ops.rope_inplace, Hq, Hk, D, CPU, gen, ref.rope_tables)
+
+
+def test_elementwise_checks_catch_wrong_kernels(gen):
+    def add_truncating(a, b):                       # rounds toward zero
+        s = (a.float() + b.float()).view(torch.int32) & ~0xFFFF
+        return s.view(torch.float32).to(torch.bfloat16)
+
+    def add_drops_last_vector(a, b):                # n8 rounded down to the block
+        c = _cpu_add(a, b)
+        c[-8:] = 0
+        return c
+
+    _rejected(ko.check_add_bf16, add_truncating, 8, CPU, gen)
+    _rejected(ko.check_add_bf16, add_drops_last_vector, 2056, CPU, gen)
+
+    def norm_unrounded_residual(x, res, w, eps):    # y from the fp32 sum, res_out one ulp off
+        y, r = _cpu_fused(x, res.clone(), w, eps)
+        r[0, 0] = _next_bf16(r[0, 0])
+        return y, r
+
+    def norm_mean_over_2048(x, w, eps):             # hidden rounded down to 256 threads x 8
+        h = max(8, x.shape[-1] // 2048 * 2048)
+        xf = x.float()
+        ms = xf[:, :h].pow(2).sum(-1, keepdim=True) / x.shape[-1]
+        return (xf * torch.rsqrt(ms + eps) * w.float()).to(x.dtype)
+
+    def norm_w_shifted(x, w, eps):                  # second pass reads w one vector late
+        return ops.rmsnorm(x, torch.roll(w, 8), eps)
+
+    _rejected(ko.check_fused_add_rmsnorm, norm_unrounded_residual, 3, 2056, CPU, gen)
+    _rejected(ko.check_rmsnorm, norm_mean_over_2048, 3, 2056, CPU, gen)
+    _rejected(ko.check_rmsnorm, norm_w_shifted, 1, 2056, CPU, gen)
+
+    def swiglu_bf16_silu(gu):                       # silu rounded to bf16 before * up
+        i = gu.shape[-1] // 2
+        s = torch.nn.functional.silu(gu[..., :i].float()).to(torch.bfloat16)
+        return (s.float() * gu[..., i:].float()).to(torch.bfloat16)
+
+    def pad_not_zeroed(gu, out_rows):
+        y = _cpu_swiglu_padded(gu, out_rows)
+        if out_rows > gu.shape[0]:
+            y[-1, -1] = -0.0
+        return y
+
+    _rejected(ko.check_swiglu, swiglu_bf16_silu, _cpu_swiglu_padded, 3, 2056, CPU, gen)
+    _rejected(ko.check_swiglu, ops.swiglu, pad_not_zeroed, 3, 2056, CPU, gen)
+
+    def rope_wrong_sign(q, k, cs, pos):             # rotates the other way
+        cs = cs.clone()
+        cs[:, cs.shape[1] // 2:] *= -1
+        ops.rope_inplace(q, k, cs, pos)
+
+    def rope_skips_k(q, k, cs, pos):
+        ops.rope_inplace(q, k.clone(), cs, pos)
+
+    _rejected(ko.check_rope_inplace, rope_wrong_sign, 6, 2, 128, CPU, gen, ref.rope_tables)
+    _rejected(ko.check_rope_inplace, rope_skips_k, 6, 2, 128, CPU, gen, ref.rope_tables)
+
+
+def test_gemm_dropped_row_of_padding_rejected(gen):
+    """An operator that returns the padded row count fails on the shape."""
+    def bad(a, b):
+        c = ref.gemm_bt_ref(a, b)
+        return torch.nn.functional.pad(c, (0, 0, 0, (-c.shape[0]) % 128))
+
+    for check in GEMM_CHECKS.values():
+        _rejected(check, bad, 17, 256, 128, CPU, gen)
