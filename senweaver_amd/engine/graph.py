@@ -50,6 +50,14 @@ class DecodeGraph:
                 self.tokens, self.pos32, self.cache.k, self.cache.v,
                 self.slot, self.bt, self.ctx)
 
+    def _next_slot(self, seq: int):
+        """(position, flat KV slot) of ``seq``'s next token; allocates its
+        page if the sequence has none for it yet."""
+        pos = self.cache.seq_lens[seq]
+        self.cache._ensure_capacity(seq, pos + 1)
+        page = self.cache.block_tables[seq][pos // PAGE_SIZE]
+        return pos, page * PAGE_SIZE + pos % PAGE_SIZE
+
     def step(self, token: int, seq: int) -> torch.Tensor:
         """Decode one token for cache sequence ``seq``; returns hidden [B,H].
 
@@ -57,12 +65,10 @@ class DecodeGraph:
         logical length) and replays the captured graph.
         """
         cache = self.cache
-        pos = cache.seq_lens[seq]
-        cache._ensure_capacity(seq, pos + 1)
-        page = cache.block_tables[seq][pos // PAGE_SIZE]
+        pos, slot = self._next_slot(seq)
         self.tokens.fill_(token)
         self.pos32.fill_(pos)
-        self.slot.fill_(page * PAGE_SIZE + pos % PAGE_SIZE)
+        self.slot.fill_(slot)
         pages = cache.block_tables[seq]
         self.bt.zero_()
         self.bt[0, : len(pages)] = torch.tensor(pages, dtype=torch.int32,
@@ -83,14 +89,11 @@ class DecodeGraph:
         """
         cache = self.cache
         assert len(seqs) == self.B and len(token_ids) == self.B
-        from .kvcache import PAGE_SIZE as _PS
         poss, slots, cts = [], [], []
         for sq in seqs:
-            pos = cache.seq_lens[sq]
-            cache._ensure_capacity(sq, pos + 1)
-            page = cache.block_tables[sq][pos // _PS]
+            pos, slot = self._next_slot(sq)
             poss.append(pos)
-            slots.append(page * _PS + pos % _PS)
+            slots.append(slot)
             cts.append(pos + 1)
         dev = self.tokens.device
         self.tokens.copy_(torch.tensor(token_ids, dtype=torch.long))

@@ -17,14 +17,12 @@ from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional
+from typing import TYPE_CHECKING, Callable, List, Optional
 
 import torch
 
 from .. import ops
 from .config import ModelConfig
-
-from typing import TYPE_CHECKING
 
 if TYPE_CHECKING:  # avoids the engine<->models import cycle
     from ..engine.kvcache import PagedKVCache
@@ -155,6 +153,9 @@ class LlamaModel:
             self.lm_head_q, self.lm_head_s = qfn(self.lm_head)
         self.cos_sin = ops.rope_tables(c.max_position, c.head_dim, c.rope_theta).to(self.device)
         self.scale = 1.0 / math.sqrt(c.head_dim)
+        # per-layout memos of plan_tensors / _down_rows (64 entries, then clear)
+        self._plan_cache = {}
+        self._down_rows_cache = {}
         if self.quant == "bf16" and self.device.type == "cuda":
             # the GEMM tuner times a projection on the weights of ALL layers
             # in turn (cold from HBM, as in a forward), not on one hot buffer
@@ -163,20 +164,45 @@ class LlamaModel:
                 for name in ("qkv", "o", "gateup", "down") if name in self.layers[0]]
 
     def _linear(self, x: torch.Tensor, L: dict, name: str) -> torch.Tensor:
-        """Projection through bf16 MFMA or the fp8 MFMA path."""
-        if self.quant == "fp8":
-            if x.shape[0] <= 8 and x.is_cuda and x.shape[-1] % 1024 == 0:
-                # decode: fp8-weight GEMV, activations stay bf16 (no
-                # per-step quant kernel, half the weight stream)
-                return ops.gemv_fp8w(x, L[name + "_q"], L[name + "_s"])
-            xq, xs = ops.quant_fp8(x)
-            return ops.gemm_bt_fp8(xq, xs, L[name + "_q"], L[name + "_s"])
-        if self.quant == "mxfp8":
-            if x.shape[0] <= 8 and x.is_cuda and x.shape[-1] % 1024 == 0:
-                return ops.gemv_mxfp8w(x, L[name + "_q"], L[name + "_s"])
-            xq, xs = ops.quant_mxfp8(x)
-            return ops.gemm_bt_mxfp8(xq, xs, L[name + "_q"], L[name + "_s"])
-        return ops.gemm_bt(x, L[name])
+        """Projection through bf16 MFMA or the fp8 MFMA path.  ``L`` holds
+        the weight as ``name``, or ``name_q`` / ``name_s`` on a quantized
+        model: a layer dict, or ``vars(self)`` for the lm_head."""
+        if self.quant == "bf16":
+            return ops.gemm_bt(x, L[name])
+        w_q, w_s = L[name + "_q"], L[name + "_s"]
+        fp8 = self.quant == "fp8"
+        if x.shape[0] <= 8 and x.is_cuda and x.shape[-1] % 1024 == 0:
+            # decode: quantized-weight GEMV, activations stay bf16 (no
+            # per-step quant kernel, no M-pad, half the weight stream)
+            return (ops.gemv_fp8w if fp8 else ops.gemv_mxfp8w)(x, w_q, w_s)
+        xq, xs = (ops.quant_fp8 if fp8 else ops.quant_mxfp8)(x)
+        return (ops.gemm_bt_fp8 if fp8 else ops.gemm_bt_mxfp8)(xq, xs, w_q, w_s)
+
+    def _layers(self, hidden: torch.Tensor,
+                attend: Callable[[int, dict, torch.Tensor], torch.Tensor],
+                full_rows: Optional[int] = None) -> torch.Tensor:
+        """The residual stream, shared by every forward path: embedded rows
+        [R, H] -> final-normed hidden states [R, H].  Per layer: pre-norm,
+        qkv projection, the path's attention stage, TP all-reduce, post-norm,
+        FFN.  ``attend(li, L, qkv)`` does everything between the qkv and the
+        o projection inclusive and returns the o projection's partial sum
+        [R, H].  ``full_rows`` (prefix-packed prefill): the unpacked row
+        count, from which _down_rows picks the down projection's."""
+        c = self.config
+        residual = None
+        for li, L in enumerate(self.layers):
+            if residual is None:
+                residual = hidden.clone()
+                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
+            else:
+                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
+            qkv = self._linear(h, L, "qkv")  # [R, local q+2kv]
+            o = attend(li, L, qkv)
+            self.tp.all_reduce_(o)  # row-parallel o_proj partial sum
+            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
+            down_rows = None if full_rows is None else self._down_rows(h, L, full_rows)
+            hidden = self._ffn(h, L, down_rows=down_rows)
+        return ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
 
     # ------------------------------------------------------------------
     # Prefill: tokens [B, S] -> final hidden states [B, S, H].
@@ -192,15 +218,7 @@ class LlamaModel:
         flat = tokens.reshape(T)
         positions = torch.arange(S, device=self.device, dtype=torch.int32).repeat(B)
 
-        hidden = self.embed[flat.long()]  # [T, H]
-        residual = None
-        for li, L in enumerate(self.layers):
-            if residual is None:
-                residual = hidden.clone()
-                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
-            else:
-                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
-            qkv = self._linear(h, L, "qkv")  # [T, local q+2kv]
+        def attend(li, L, qkv):
             qs, kvs = self.local_q_size, self.local_kv_size
             # fused rope + [B,H,S,D] scatter reading the qkv slices in place
             qb, kb = ops.rope_scatter_qkv(qkv, self.cos_sin, positions,
@@ -223,20 +241,14 @@ class LlamaModel:
                 if self.quant == "bf16":
                     # o_proj directly off the O^T view: hipBLASLt takes the
                     # transposed A natively — no [T, qsize] copy materialized
-                    o = ops.gemm_bt_heads_t(ot.reshape(B, self.local_q_size, S), L["o"])
-                    self.tp.all_reduce_(o)
-                    h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-                    hidden = self._ffn(h, L)
-                    continue
+                    return ops.gemm_bt_heads_t(ot.reshape(B, self.local_q_size, S), L["o"])
                 attn = ot.permute(0, 3, 1, 2).reshape(T, self.local_q_size).contiguous()
             else:  # v1 kernel path for 64-granular sequences
                 ab = ops.attn_fwd(qb, kb, None, self.scale, vt=vt)
                 attn = ab.transpose(1, 2).reshape(T, self.local_q_size).contiguous()
-            o = self._linear(attn, L, "o")
-            self.tp.all_reduce_(o)  # row-parallel o_proj partial sum
-            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-            hidden = self._ffn(h, L)
-        h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
+            return self._linear(attn, L, "o")
+
+        h = self._layers(self.embed[flat.long()], attend)  # [T, H]
         return h.reshape(B, S, c.hidden_size)
 
     # ------------------------------------------------------------------
@@ -253,7 +265,7 @@ class LlamaModel:
         """Device copies of a plan (skip, base, owner int32 [B]; positions
         int32 [Tp]; flat token index int64 [Tp]), cached per layout: the
         scorer sees the same layout for every candidate of a step."""
-        cache = self.__dict__.setdefault("_plan_cache", {})
+        cache = self._plan_cache
         key = (plan.S, plan.owner, plan.skip)
         hit = cache.get(key)
         if hit is None:
@@ -283,15 +295,7 @@ class LlamaModel:
             # take: the unpacked path, handed back in packed-row order
             return self.prefill(tokens).reshape(B * S, -1)[flat_idx]
 
-        hidden = self.embed[tokens.reshape(B * S)[flat_idx]]  # [Tp, H]
-        residual = None
-        for L in self.layers:
-            if residual is None:
-                residual = hidden.clone()
-                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
-            else:
-                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
-            qkv = self._linear(h, L, "qkv")  # [Tp, local q+2kv]
+        def attend(li, L, qkv):
             qb, kb = ops.rope_scatter_qkv_packed(
                 qkv, self.cos_sin, positions, self.local_heads,
                 self.local_kv_heads, c.head_dim, B, S, skip, base, owner)
@@ -306,13 +310,11 @@ class LlamaModel:
             if self.quant == "bf16" and not attn.is_cuda:
                 # CPU: the bf16 matmul the unpacked path's o_proj uses, so
                 # packed and unpacked stay bit-equal there
-                o = torch.matmul(attn, L["o"].t())
-            else:
-                o = self._linear(attn, L, "o")
-            self.tp.all_reduce_(o)
-            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-            hidden = self._ffn(h, L, down_rows=self._down_rows(h, L, B * S))
-        return ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
+                return torch.matmul(attn, L["o"].t())
+            return self._linear(attn, L, "o")
+
+        hidden = self.embed[tokens.reshape(B * S)[flat_idx]]  # [Tp, H]
+        return self._layers(hidden, attend, full_rows=B * S)
 
     def _down_rows(self, h: torch.Tensor, L: dict, full_rows: int) -> Optional[int]:
         """Row count for the packed path's down projection: Tp, or the
@@ -328,7 +330,7 @@ class LlamaModel:
         Tp = h.shape[0]
         if self.quant != "bf16" or "down" not in L or full_rows <= Tp:
             return None
-        cache = self.__dict__.setdefault("_down_rows_cache", {})
+        cache = self._down_rows_cache
         hit = cache.get((Tp, full_rows), 0)
         if hit == 0:
             hit = full_rows
@@ -389,17 +391,7 @@ class LlamaModel:
         k = c.num_experts_per_tok
         if self.quant in ("fp8", "mxfp8"):
             return self._moe_ffn_fp8(h, L)
-        # router is [E=8, H]: far below the MFMA tile (N=8) — a plain skinny
-        # library matmul, not a hot op
-        router_logits = h @ L["router"].t()  # [T, E]
-        probs = torch.softmax(router_logits.float(), dim=-1)
-        topw, topi = probs.topk(k, dim=-1)           # [T, k]
-        topw = topw / topw.sum(dim=-1, keepdim=True)  # renormalize (Mixtral)
-        flat_expert = topi.reshape(-1)                # [T*k]
-        flat_token = torch.arange(T, device=h.device).repeat_interleave(k)
-        order = torch.argsort(flat_expert, stable=True)
-        sorted_token = flat_token[order]
-        sorted_weight = topw.reshape(-1)[order]
+        flat_expert, order, sorted_token, sorted_weight = self._route(h, L)
         counts = torch.bincount(flat_expert, minlength=c.num_experts)
         Tk = T * k
         if self.ep.world > 1:
@@ -409,28 +401,15 @@ class LlamaModel:
             x_local, local_counts, meta = self.ep.dispatch(
                 a_sorted, counts, c.num_experts)
             Tl = x_local.shape[0]
-            pad = 128
-            a_p = torch.zeros(Tl + pad, c.hidden_size, dtype=h.dtype,
-                              device=h.device)
-            a_p[:Tl] = x_local
+            a_p = self._pad128(x_local)
             seg = [0]
             for e in range(local_counts.shape[0]):
                 seg.append(seg[-1] + int(local_counts[e]))
             gateup = ops.grouped_gemm_bt(a_p, L["w13"], seg)
             act = ops.swiglu(gateup[:Tl])
-            act_p = torch.zeros(Tl + pad, act.shape[1], dtype=h.dtype,
-                                device=h.device)
-            act_p[:Tl] = act
-            down_l = ops.grouped_gemm_bt(act_p, L["w2"], seg)[:Tl]
+            down_l = ops.grouped_gemm_bt(self._pad128(act), L["w2"], seg)[:Tl]
             down = self.ep.combine(down_l, meta)
-            res = torch.zeros(T, c.hidden_size, dtype=torch.float32,
-                              device=h.device)
-            res.index_add_(0, sorted_token,
-                           down.float() * sorted_weight.unsqueeze(-1).float())
-            out = res.to(h.dtype)
-            self.tp.all_reduce_(out)  # row-parallel w2 partial sum (TP x EP)
-            return out
-        if h.is_cuda:
+        elif h.is_cuda:
             # sync-free routing: device-side cumulative ends feed the grouped
             # GEMM directly (the per-expert int(counts[e]) reads were 8 tiny
             # D2H syncs per MoE layer, visible as copyBuffer storms in the
@@ -451,19 +430,50 @@ class LlamaModel:
             seg_starts = [0]
             for e in range(c.num_experts):
                 seg_starts.append(seg_starts[-1] + int(counts[e]))
-            pad = 128  # last-tile overread margin for the grouped kernel
-            a_sorted = torch.zeros(Tk + pad, c.hidden_size, dtype=h.dtype, device=h.device)
-            a_sorted[:Tk] = h[sorted_token]
+            a_sorted = self._pad128(h[sorted_token])
             gateup = ops.grouped_gemm_bt(a_sorted, L["w13"], seg_starts)
             act = ops.swiglu(gateup[:Tk])
-            act_p = torch.zeros(Tk + pad, act.shape[1], dtype=h.dtype, device=h.device)
-            act_p[:Tk] = act
-            down = ops.grouped_gemm_bt(act_p, L["w2"], seg_starts)[:Tk]
-        out = torch.zeros(T, c.hidden_size, dtype=torch.float32, device=h.device)
-        out.index_add_(0, sorted_token, down.float() * sorted_weight.unsqueeze(1))
-        res = out.to(h.dtype)
-        self.tp.all_reduce_(res)  # row-parallel down partial sum (TP)
+            down = ops.grouped_gemm_bt(self._pad128(act), L["w2"], seg_starts)[:Tk]
+        res = self._combine_f32(h, down, sorted_token, sorted_weight)
+        self.tp.all_reduce_(res)  # row-parallel w2 partial sum (TP, TP x EP)
         return res
+
+    def _route(self, h: torch.Tensor, L: dict):
+        """Top-k routing of h [T, H], shared by both routed FFNs.  Returns
+        (flat_expert [T*k] in token order, order: its stable argsort,
+        sorted_token / sorted_weight [T*k]: token row and renormalised f32
+        router weight of every slot in expert-sorted order)."""
+        T = h.shape[0]
+        k = self.config.num_experts_per_tok
+        # router is [E=8, H]: far below the MFMA tile (N=8) — a plain skinny
+        # library matmul, not a hot op
+        router_logits = h @ L["router"].t()  # [T, E]
+        probs = torch.softmax(router_logits.float(), dim=-1)
+        topw, topi = probs.topk(k, dim=-1)           # [T, k]
+        topw = topw / topw.sum(dim=-1, keepdim=True)  # renormalize (Mixtral)
+        flat_expert = topi.reshape(-1)                # [T*k]
+        flat_token = torch.arange(T, device=h.device).repeat_interleave(k)
+        order = torch.argsort(flat_expert, stable=True)
+        return flat_expert, order, flat_token[order], topw.reshape(-1)[order]
+
+    @staticmethod
+    def _pad128(x: torch.Tensor) -> torch.Tensor:
+        """x [R, K] copied into a zero buffer of R + 128 rows: last-tile
+        overread margin for the grouped kernel."""
+        R = x.shape[0]
+        p = torch.zeros(R + 128, x.shape[1], dtype=x.dtype, device=x.device)
+        p[:R] = x
+        return p
+
+    @staticmethod
+    def _combine_f32(h: torch.Tensor, down: torch.Tensor, sorted_token: torch.Tensor,
+                     sorted_weight: torch.Tensor) -> torch.Tensor:
+        """Weighted combine of the expert-sorted slot outputs ``down`` back
+        into token rows where the fused moe_combine kernel does not run (EP,
+        CPU): f32 zeros + index_add_, cast to h's dtype."""
+        out = torch.zeros(h.shape, dtype=torch.float32, device=h.device)
+        out.index_add_(0, sorted_token, down.float() * sorted_weight.unsqueeze(1))
+        return out.to(h.dtype)
 
     def _moe_ffn_fp8(self, h: torch.Tensor, L: dict) -> torch.Tensor:
         """fp8 routed FFN: expert-sorted tokens in 16-ALIGNED padded segments
@@ -473,15 +483,7 @@ class LlamaModel:
         c = self.config
         T = h.shape[0]
         k = c.num_experts_per_tok
-        router_logits = h @ L["router"].t()
-        probs = torch.softmax(router_logits.float(), dim=-1)
-        topw, topi = probs.topk(k, dim=-1)
-        topw = topw / topw.sum(dim=-1, keepdim=True)
-        flat_expert = topi.reshape(-1)
-        flat_token = torch.arange(T, device=h.device).repeat_interleave(k)
-        order = torch.argsort(flat_expert, stable=True)
-        sorted_token = flat_token[order]
-        sorted_weight = topw.reshape(-1)[order]
+        flat_expert, order, sorted_token, sorted_weight = self._route(h, L)
         sorted_expert = flat_expert[order]
         # one D2H transfer for all expert counts (16-aligned padding needs
         # host-side sizes; the bf16 path is fully sync-free)
@@ -513,9 +515,7 @@ class LlamaModel:
             w_pad[dest] = sorted_weight.float()
             res = ops.hip_ext().moe_combine(down.contiguous(), inv_pad, w_pad)
         else:
-            out = torch.zeros(T, c.hidden_size, dtype=torch.float32, device=dev)
-            out.index_add_(0, sorted_token, down[dest].float() * sorted_weight.unsqueeze(1))
-            res = out.to(h.dtype)
+            res = self._combine_f32(h, down[dest], sorted_token, sorted_weight)
         self.tp.all_reduce_(res)  # row-parallel down partial sum (TP)
         return res
 
@@ -534,32 +534,8 @@ class LlamaModel:
         """
         c = self.config
         B = tokens.shape[0]
-        hidden = self.embed[tokens]
-        residual = None
-        # fused add+norm+GEMV path: bf16 dense decode with GEMV-eligible
-        # shapes (one kernel replaces fused_add_rmsnorm + gemv per norm)
-        # add+norm+GEMV fusion measured SLOWER (206 vs 218 tok/s same box):
-        # every GEMV wave re-reads x/res/normw rows from L2 (3 rows instead
-        # of 1), outweighing the two saved ~5us launches per layer.  Kept
-        # behind the env switch as a logged A/B (profiles/r01_pmc_summary).
-        import os as _os
-        fuse_ng = (self.quant == "bf16" and B <= 16
-                   and _os.environ.get("SENWEAVER_DECODE_NORMFUSE", "0") == "1"
-                   and c.hidden_size % 512 == 0
-                   and (self.local_q_size + 2 * self.local_kv_size) % 4 == 0
-                   and 2 * self.local_inter % 4 == 0)
-        for li, L in enumerate(self.layers):
-            if fuse_ng:
-                qkv, residual = ops.gemv_norm_bt(hidden, residual,
-                                                 L["input_norm"], L["qkv"],
-                                                 c.rms_eps)
-            else:
-                if residual is None:
-                    residual = hidden.clone()
-                    h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
-                else:
-                    h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
-                qkv = self._linear(h, L, "qkv")
+
+        def attend(li, L, qkv):
             P = kcaches[li].shape[0]
             # fused slice+rope+cache-append (one kernel instead of six)
             q = ops.rope_kv_append(
@@ -568,13 +544,37 @@ class LlamaModel:
                 vcaches[li].view(P * 16, self.local_kv_heads, c.head_dim),
                 self.local_heads, self.local_kv_heads, c.head_dim)
             attn = ops.paged_decode_attn(q, kcaches[li], vcaches[li], bt, ctx, self.scale)
-            attn = attn.reshape(B, self.local_q_size)
-            o = self._linear(attn, L, "o")
+            return self._linear(attn.reshape(B, self.local_q_size), L, "o")
+
+        # fused add+norm+GEMV path: bf16 dense decode with GEMV-eligible
+        # shapes (one kernel replaces fused_add_rmsnorm + gemv per norm)
+        # add+norm+GEMV fusion measured SLOWER (206 vs 218 tok/s same box):
+        # every GEMV wave re-reads x/res/normw rows from L2 (3 rows instead
+        # of 1), outweighing the two saved ~5us launches per layer.  Kept
+        # behind the env switch as a logged A/B (profiles/r01_pmc_summary).
+        fuse_ng = (self.quant == "bf16" and B <= 16
+                   and os.environ.get("SENWEAVER_DECODE_NORMFUSE", "0") == "1"
+                   and c.hidden_size % 512 == 0
+                   and (self.local_q_size + 2 * self.local_kv_size) % 4 == 0
+                   and 2 * self.local_inter % 4 == 0)
+        layers = self._layers_normfuse if fuse_ng else self._layers
+        return layers(self.embed[tokens], attend)
+
+    def _layers_normfuse(self, hidden: torch.Tensor, attend) -> torch.Tensor:
+        """EXPERIMENT (SENWEAVER_DECODE_NORMFUSE=1, decode_step_tensors only):
+        _layers with gemv_norm_bt in place of norm + GEMV before the qkv and
+        the dense gate|up projection.  The fusion crosses the seams of the
+        shared loop, hence this copy of it."""
+        c = self.config
+        residual = None
+        for li, L in enumerate(self.layers):
+            qkv, residual = ops.gemv_norm_bt(hidden, residual, L["input_norm"],
+                                             L["qkv"], c.rms_eps)
+            o = attend(li, L, qkv)
             self.tp.all_reduce_(o)
-            if fuse_ng and c.num_experts == 0:
-                gateup, residual = ops.gemv_norm_bt(o, residual,
-                                                    L["post_norm"], L["gateup"],
-                                                    c.rms_eps)
+            if c.num_experts == 0:
+                gateup, residual = ops.gemv_norm_bt(o, residual, L["post_norm"],
+                                                    L["gateup"], c.rms_eps)
                 act = ops.swiglu(gateup)
                 hidden = self._linear(act, L, "down")
                 self.tp.all_reduce_(hidden)
@@ -588,18 +588,13 @@ class LlamaModel:
         c = self.config
         B = tokens.shape[0]
         hidden = self.embed[tokens.long()]
-        residual = None
         pos32 = positions.to(torch.int32)
         # context length for this token, captured before any append
         ctx_vals = [cache.seq_lens[s] + 1 for s in seqs]
         bt = ctx = None
-        for li, L in enumerate(self.layers):
-            if residual is None:
-                residual = hidden.clone()
-                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
-            else:
-                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
-            qkv = self._linear(h, L, "qkv")
+
+        def attend(li, L, qkv):
+            nonlocal bt, ctx
             qs, kvs = self.local_q_size, self.local_kv_size
             q = qkv[:, :qs].reshape(B, self.local_heads, c.head_dim).contiguous()
             k = qkv[:, qs: qs + kvs].reshape(B, self.local_kv_heads, c.head_dim).contiguous()
@@ -614,13 +609,9 @@ class LlamaModel:
                 bt = cache.block_table_tensor(seqs)
                 ctx = torch.tensor(ctx_vals, dtype=torch.int32, device=self.device)
             attn = ops.paged_decode_attn(q, cache.k[li], cache.v[li], bt, ctx, self.scale)
-            attn = attn.reshape(B, self.local_q_size)
-            o = self._linear(attn, L, "o")
-            self.tp.all_reduce_(o)
-            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-            hidden = self._ffn(h, L)
-        h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
-        return h  # [B, hidden]
+            return self._linear(attn.reshape(B, self.local_q_size), L, "o")
+
+        return self._layers(hidden, attend)  # [B, hidden]
 
     # ------------------------------------------------------------------
     # Extend: append new_lens[b] tokens to sequences that already hold
@@ -660,16 +651,9 @@ class LlamaModel:
                            dtype=torch.int32, device=dev)
         qlen = torch.tensor(new_lens, dtype=torch.int32, device=dev)
 
-        hidden = self.embed[tokens.reshape(B * Sq).long()]
-        residual = None
         Hq, Hk, D = self.local_heads, self.local_kv_heads, c.head_dim
-        for li, L in enumerate(self.layers):
-            if residual is None:
-                residual = hidden.clone()
-                h = ops.rmsnorm(hidden, L["input_norm"], c.rms_eps)
-            else:
-                h = ops.fused_add_rmsnorm(hidden, residual, L["input_norm"], c.rms_eps)
-            qkv = self._linear(h, L, "qkv")
+
+        def attend(li, L, qkv):
             P = cache.k[li].shape[0]
             q_real = ops.rope_kv_append(
                 qkv if real_idx is None else qkv[real_idx],
@@ -684,28 +668,13 @@ class LlamaModel:
                 q = q.reshape(B, Sq, Hq, D)
             attn = ops.paged_prefill_attn(q, cache.k[li], cache.v[li], bt, ctx,
                                           qlen, self.scale)
-            o = self._linear(attn.reshape(B * Sq, self.local_q_size), L, "o")
-            self.tp.all_reduce_(o)
-            h = ops.fused_add_rmsnorm(o, residual, L["post_norm"], c.rms_eps)
-            hidden = self._ffn(h, L)
+            return self._linear(attn.reshape(B * Sq, self.local_q_size), L, "o")
+
+        h = self._layers(self.embed[tokens.reshape(B * Sq).long()], attend)
         for b in range(B):
             cache.seq_lens[seqs[b]] = starts[b] + new_lens[b]
-        h = ops.fused_add_rmsnorm(hidden, residual, self.final_norm, c.rms_eps)
         return h.reshape(B, Sq, c.hidden_size)
 
     def logits(self, hidden: torch.Tensor) -> torch.Tensor:
         """hidden [*, H] -> logits [*, vocab] through the lm_head GEMM."""
-        flat = hidden.reshape(-1, self.config.hidden_size)
-        small = flat.shape[0] <= 8 and flat.is_cuda and \
-            flat.shape[-1] % 1024 == 0
-        if self.quant == "fp8":
-            if small:  # decode: quantized-weight GEMV (no act quant, no M-pad)
-                return ops.gemv_fp8w(flat, self.lm_head_q, self.lm_head_s)
-            xq, xs = ops.quant_fp8(flat)
-            return ops.gemm_bt_fp8(xq, xs, self.lm_head_q, self.lm_head_s)
-        if self.quant == "mxfp8":
-            if small:
-                return ops.gemv_mxfp8w(flat, self.lm_head_q, self.lm_head_s)
-            xq, xs = ops.quant_mxfp8(flat)
-            return ops.gemm_bt_mxfp8(xq, xs, self.lm_head_q, self.lm_head_s)
-        return ops.gemm_bt(flat, self.lm_head)
+        return self._linear(hidden.reshape(-1, self.config.hidden_size), vars(self), "lm_head")

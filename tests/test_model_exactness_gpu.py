@@ -130,6 +130,15 @@ def test_decode_single_graph(dev, quant, ext_calls):
     assert gemv_binding[quant] in ext_calls and "paged_decode_attn" in ext_calls
 
 
+def test_decode_single_graph_normfuse(dev, ext_calls, monkeypatch):
+    """SENWEAVER_DECODE_NORMFUSE=1: gemv_norm_bt in place of norm + GEMV
+    before the qkv and the gate|up projection, same bound."""
+    monkeypatch.setenv("SENWEAVER_DECODE_NORMFUSE", "1")
+    mo.run_decode(gemv(dev), mo.dense_tokens(2, 128)[1:], REAL_LENS[1:],
+                  FORCED[1:], "graph1", "decode graph gemv bf16 B=1 NORMFUSE")
+    assert "gemv_norm_bt" in ext_calls
+
+
 def test_prefill_extend(dev):
     mo.run_extend(gemv(dev), mo.dense_tokens(1, 137, seed=13), 100, 37,
                   "prefill_extend gemv 100+37")
