@@ -123,7 +123,7 @@ def bench_gemm_lt(argv):
 
 
 def bench_gemm8():
-    """A/B: 8-phase pipelined kernel vs the old 256-tile vs hipBLASLt."""
+    """The pipelined 256-tile kernels (v14, asm4 = 21, asm7 = 24) vs hipBLASLt."""
     dev = torch.device("cuda:0")
     ext = ops.hip_ext()
     shapes = [
@@ -138,17 +138,18 @@ def bench_gemm8():
         a = torch.randn(M, K, dtype=torch.bfloat16, device=dev)
         b = torch.randn(N, K, dtype=torch.bfloat16, device=dev)
         fl = 2 * M * N * K / 1e12
-        t8 = timeit(lambda: ext.gemm_bt_8ph(a, b))
+        ts = {var: timeit(lambda: ext.gemm_bt_8ph_v(a, b, var)) for var in (14, 21, 24)}
         tb = timeit(lambda: a @ b.t())
-        print(f"GEMM8 {M}x{N}x{K}: 8ph {fl / t8:7.1f} TF/s   "
-              f"hipblaslt {fl / tb:7.1f} TF/s")
+        print(f"GEMM8 {M}x{N}x{K}: " +
+              "  ".join(f"v{var} {fl / t:7.1f}" for var, t in ts.items()) +
+              f" TF/s   hipblaslt {fl / tb:7.1f} TF/s")
         # numerics spot-check on the fly (fp32 reference is expensive at 8k;
         # compare vs blas bf16 result within bf16 tolerance)
-        c8 = ext.gemm_bt_8ph(a, b).float()
         cb = (a @ b.t()).float()
-        err = (c8 - cb).abs().max().item()
         den = cb.abs().max().item()
-        print(f"      max|d| {err:.3f} (ref max {den:.1f})")
+        for var in ts:
+            err = (ext.gemm_bt_8ph_v(a, b, var).float() - cb).abs().max().item()
+            print(f"      v{var} max|d| {err:.3f} (ref max {den:.1f})")
 
 
 def bench_fp8():

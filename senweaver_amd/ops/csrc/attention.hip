@@ -18,6 +18,7 @@
 // masked rows via the causal mask: rows >= S_real are never read back).
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

@@ -23,6 +23,7 @@
 // 3 waves/SIMD).  D = 128, causal, GQA.  S % 128 == 0.
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -20,6 +20,7 @@
 // reference in tests/test_kernels_gpu.py.
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -6,82 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-
-// ---- kernel prototypes (defined in the sibling .hip translation units) ----
-extern "C" __global__ void rmsnorm_fwd_kernel(const ushort*, const ushort*, ushort*, ushort*, int, float);
-extern "C" __global__ void rope_fwd_kernel(ushort*, ushort*, const float*, const int*, int, int, int);
-extern "C" __global__ void rope_scatter_kernel(const ushort*, long long, ushort*, ushort*, const float*, const int*, int, int, int, int);
-extern "C" __global__ void transpose_v_kernel(const ushort*, long long, long long, ushort*, int, int, int, int);
-extern "C" __global__ void rope_kv_append_kernel(const ushort*, long long, ushort*, ushort*, ushort*, const float*, const int*, const int*, int, int, int);
-extern "C" __global__ void swiglu_fwd_kernel(const ushort*, ushort*, long long, int);
-extern "C" __global__ void add_bf16_kernel(const ushort*, const ushort*, ushort*, long long);
-extern "C" __global__ void argmax_rows_kernel(const ushort*, int*, int);
-extern "C" __global__ void target_logprob_kernel(const ushort*, const int*, float*, int);
-extern "C" __global__ void gemm_bt_bf16_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_256_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_256x32_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_256sg_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v1_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v2_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v3_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v4_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v5_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v6_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v7_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v8_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v9_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v11_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v12_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v13_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v14_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v16_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_8ph_v17_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm2_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm3_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm4_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm5_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm6_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_bf16_asm7_kernel(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void grouped_gemm_bt_bf16_kernel(const ushort*, const ushort*, ushort*, const int*, const int*, const int*, int, int, int);
-extern "C" __global__ void moe_combine_kernel(const ushort*, const int*, const float*, ushort*, int, int);
-extern "C" __global__ void quant_fp8_rowwise_kernel(const ushort*, unsigned char*, float*, int);
-extern "C" __global__ void gemm_bt_fp8_kernel(const unsigned char*, const float*, const unsigned char*, const float*, ushort*, int, int, int);
-extern "C" __global__ void quant_mxfp8_kernel(const ushort*, unsigned char*, unsigned char*, int);
-extern "C" __global__ void gemm_bt_mxfp8_kernel(const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_mxfp8_256_kernel(const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemm_bt_mxfp8_pipe_kernel(const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v2_m1(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v3_m1(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_fp8w_m1(const ushort*, const unsigned char*, const float*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_fp8w_m2(const ushort*, const unsigned char*, const float*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_fp8w_m4(const ushort*, const unsigned char*, const float*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_fp8w_m8(const ushort*, const unsigned char*, const float*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_mxfp8w_m1(const ushort*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_mxfp8w_m2(const ushort*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_mxfp8w_m4(const ushort*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_mxfp8w_m8(const ushort*, const unsigned char*, const unsigned char*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v3w_m1(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void swiglu_gemv_bt_bf16_m1(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v2_m2(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v2_m4(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v2_m8(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_bt_bf16_v2_m16(const ushort*, const ushort*, ushort*, int, int, int);
-extern "C" __global__ void gemv_norm_bt_bf16_m1(const ushort*, const ushort*, const ushort*, const ushort*, ushort*, ushort*, int, int, int, float);
-extern "C" __global__ void gemv_norm_bt_bf16_m2(const ushort*, const ushort*, const ushort*, const ushort*, ushort*, ushort*, int, int, int, float);
-extern "C" __global__ void gemv_norm_bt_bf16_m4(const ushort*, const ushort*, const ushort*, const ushort*, ushort*, ushort*, int, int, int, float);
-extern "C" __global__ void gemv_norm_bt_bf16_m8(const ushort*, const ushort*, const ushort*, const ushort*, ushort*, ushort*, int, int, int, float);
-extern "C" __global__ void gemv_norm_bt_bf16_m16(const ushort*, const ushort*, const ushort*, const ushort*, ushort*, ushort*, int, int, int, float);
-extern "C" __global__ void attn_fwd_bf16_kernel(const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int, float);
-extern "C" __global__ void attn_fwd_v2_kernel(const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int, float);
-extern "C" __global__ void attn_fwd_v3_kernel(const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int, float);
-extern "C" __global__ void paged_decode_attn_partial_kernel(const ushort*, const ushort*, const ushort*, float*,
-                                                            const int*, const int*, int, int, int, float);
-extern "C" __global__ void paged_decode_attn_merge_kernel(const float*, ushort*, int);
-extern "C" __global__ void paged_prefill_attn_kernel(const ushort*, const ushort*, const ushort*, ushort*,
-                                                     const int*, const int*, const int*,
-                                                     int, int, int, int, float);
+#include "kernels.h"
 
 namespace {
 
@@ -119,14 +44,13 @@ GemmDims check_gemm_operands(const torch::Tensor& a, const torch::Tensor& b,
   return {(int)a.size(0), (int)b.size(0), (int)a.size(1)};
 }
 
-// The 256 x 256-tile bindings: whole tiles only, K a positive multiple of
-// kmult (128 for the counted-vmcnt pipelines, whose prologues need two
-// 64-wide K-tiles; 64 for the full-drain double-buffer kernels).
+// gemm_bt_8ph_v: whole 256 x 256 tiles only, K a positive multiple of 128
+// (the counted-vmcnt pipelines' prologues need two 64-wide K-tiles).
 GemmDims check_gemm_256(const torch::Tensor& a, const torch::Tensor& b,
-                        const char* op, int kmult) {
+                        const char* op) {
   const GemmDims d = check_gemm_operands(a, b, op);
-  TORCH_CHECK(d.M % 256 == 0 && d.N % 256 == 0 && d.K >= kmult && d.K % kmult == 0,
-              op, " needs M, N % 256 == 0 and K a positive multiple of ", kmult,
+  TORCH_CHECK(d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 128 && d.K % 128 == 0,
+              op, " needs M, N % 256 == 0 and K a positive multiple of 128",
               "; got ", d.M, "x", d.N, "x", d.K);
   return d;
 }
@@ -715,20 +639,6 @@ torch::Tensor attn_fwd_v5(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
 // skip/base/owner: the per-batch-row layout plan (csrc/README.md, "Packed
 // prefill layout").  They live on the device, so only their form is checked
 // here; the kernels drop any row a bad plan would send out of bounds.
-extern "C" __global__ void rope_scatter_packed_kernel(
-    const ushort*, long long, ushort*, ushort*, const float*, const int*, int,
-    int, int, int, int, const int*, const int*, const int*, long long);
-extern "C" __global__ void transpose_v_packed_kernel(
-    const ushort*, long long, long long, ushort*, int, int, int, int,
-    const int*, const int*, const int*, long long);
-extern "C" __global__ void attn_fwd_v5_packed_kernel(
-    const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int,
-    float, const int*, const int*, int);
-
-extern "C" __global__ void attn_fwd_v5_packed_rm_kernel(
-    const ushort*, const ushort*, const ushort*, ushort*, int, int, int, int,
-    float, const int*, const int*, int);
-
 static void check_plan(const torch::Tensor& t, int64_t B, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
                   t.is_contiguous() && t.dim() == 1 && t.size(0) == B,
@@ -958,74 +868,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "swiglu into [out_rows, inter]; rows past the input's are zero");
   m.def("add_bf16", &add_bf16, "a + b (bf16)");
   m.def("gemm_bt", &gemm_bt, "C = A @ B^T (bf16 MFMA)");
-  m.def("gemm_bt_8ph", [](torch::Tensor a, torch::Tensor b) {
-    const GemmDims d = check_gemm_256(a, b, "gemm_bt_8ph", 128);
-    const int M = d.M, K = d.K, N = d.N;
-    auto C = torch::empty({M, N}, a.options());
-    gemm_bt_bf16_8ph_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
-        bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);
-    HIP_CHECK_KERNEL();
-    return C;
-  }, "256-tile 8-phase deep-pipelined GEMM (counted vmcnt)");
   m.def("gemm_bt_8ph_v", [](torch::Tensor a, torch::Tensor b, long var) {
-    const GemmDims d = check_gemm_256(a, b, "gemm_bt_8ph_v", 128);
+    const GemmDims d = check_gemm_256(a, b, "gemm_bt_8ph_v");
     const int M = d.M, K = d.K, N = d.N;
     auto C = torch::empty({M, N}, a.options());
-    const dim3 g((M / 256) * (N / 256)), blk(512);
+    const dim3 g((M / 256) * (N / 256));
     switch (var) {
-      case 1: gemm_bt_bf16_8ph_v1_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 2: gemm_bt_bf16_8ph_v2_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 3: gemm_bt_bf16_8ph_v3_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 4: gemm_bt_bf16_8ph_v4_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 5: gemm_bt_bf16_8ph_v5_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 6: gemm_bt_bf16_8ph_v6_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 7: gemm_bt_bf16_8ph_v7_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 8: gemm_bt_bf16_8ph_v8_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 9: gemm_bt_bf16_8ph_v9_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 11: gemm_bt_bf16_8ph_v11_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 12: gemm_bt_bf16_8ph_v12_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 13: gemm_bt_bf16_8ph_v13_kernel<<<dim3((M / 256) * (N / 256)), dim3(1024), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 14: gemm_bt_bf16_8ph_v14_kernel<<<dim3((M / 256) * (N / 256)), dim3(1024), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 16: gemm_bt_bf16_8ph_v16_kernel<<<g, blk, 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 17: gemm_bt_bf16_8ph_v17_kernel<<<dim3((M / 256) * (N / 128)), dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 18: gemm_bt_bf16_asm_kernel<<<g, dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 19: gemm_bt_bf16_asm2_kernel<<<g, dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 20: gemm_bt_bf16_asm3_kernel<<<g, dim3(512), 0, cur_stream()>>>(
+      case 14: gemm_bt_bf16_8ph_v14_kernel<<<g, dim3(1024), 0, cur_stream()>>>(
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
       case 21: gemm_bt_bf16_asm4_kernel<<<g, dim3(512), 0, cur_stream()>>>(
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 22: gemm_bt_bf16_asm5_kernel<<<g, dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 23: gemm_bt_bf16_asm6_kernel<<<g, dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
       case 24: gemm_bt_bf16_asm7_kernel<<<g, dim3(512), 0, cur_stream()>>>(
-                  bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
-      case 0: gemm_bt_bf16_8ph_kernel<<<g, blk, 0, cur_stream()>>>(
                   bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K); break;
       default:
         TORCH_CHECK(false, "gemm_bt_8ph_v: unknown variant ", var,
-                    " (known: 0-9, 11-14, 16-24)");
+                    " (known: 14, 21, 24)");
     }
     HIP_CHECK_KERNEL();
     return C;
-  }, "8-phase GEMM structural variants (A/B probe)");
+  }, "the pipelined 256-tile GEMMs gemm_bt dispatches to: 14 = v14, 21 = asm4, 24 = asm7");
   m.def("gemv_bt_v3", [](torch::Tensor a, torch::Tensor b) {
     check_bf16(a, "a"); check_bf16(b, "b");
     const int M = a.size(0), K = a.size(1), N = b.size(0);
@@ -1115,24 +976,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     HIP_CHECK_KERNEL();
     return C;
   }, "fused silu(g)*u + streaming GEMV (decode down-proj, M=1)");
-  m.def("gemm_bt_256x32", [](torch::Tensor a, torch::Tensor b) {
-    const GemmDims d = check_gemm_256(a, b, "gemm_bt_256x32", 64);
-    const int M = d.M, K = d.K, N = d.N;
-    auto C = torch::empty({M, N}, a.options());
-    gemm_bt_bf16_256x32_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
-        bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);
-    HIP_CHECK_KERNEL();
-    return C;
-  }, "256-tile GEMM on 32x32x16 MFMA (A/B experiment)");
-  m.def("gemm_bt_256sg", [](torch::Tensor a, torch::Tensor b) {
-    const GemmDims d = check_gemm_256(a, b, "gemm_bt_256sg", 64);
-    const int M = d.M, K = d.K, N = d.N;
-    auto C = torch::empty({M, N}, a.options());
-    gemm_bt_bf16_256sg_kernel<<<dim3((M / 256) * (N / 256)), dim3(512), 0, cur_stream()>>>(
-        bf16_ptr(a), bf16_ptr(b), bf16_mut(C), M, N, K);
-    HIP_CHECK_KERNEL();
-    return C;
-  }, "256-tile GEMM with sched_group_barrier interleave (A/B experiment)");
   m.def("grouped_gemm_bt", &grouped_gemm_bt, "segment-grouped C = A @ W[e]^T (MoE)");
   m.def("moe_combine", [](torch::Tensor down, torch::Tensor pos, torch::Tensor weight) {
     check_bf16(down, "down");

@@ -20,6 +20,7 @@
 //     graph-capturable (no host reads, stable shapes).
 
 #include "common.h"
+#include "kernels.h"
 
 #define PAGE_SIZE 16
 #define DA_NSPLIT 8

@@ -7,6 +7,7 @@
 // kernels are the MI355X-native compute path that replaces it.
 
 #include "common.h"
+#include "kernels.h"
 
 // ---------------------------------------------------------------------------
 // RMSNorm (optionally fused with residual add).

@@ -13,6 +13,7 @@
 // fp8 numerics contract for ranking-stability testing.
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 

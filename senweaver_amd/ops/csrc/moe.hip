@@ -11,6 +11,7 @@
 // W: [E, N, K] bf16 row-major.  A_sorted: [T_pad, N? no: K].  C: [T_pad, N].
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

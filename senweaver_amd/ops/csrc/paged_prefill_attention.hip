@@ -37,6 +37,7 @@
 //     produces.
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) short short4v;

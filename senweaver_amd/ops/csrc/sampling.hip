@@ -6,6 +6,7 @@
 // produce either the argmax or log_softmax(logits)[target] directly.
 
 #include "common.h"
+#include "kernels.h"
 
 // ---------------------------------------------------------------------------
 // Row argmax over bf16 logits [rows, vocab] -> int32 [rows].

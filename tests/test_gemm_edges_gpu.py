@@ -155,27 +155,25 @@ def test_gemm_bindings_reject_mismatched_operands(dev):
     b_wide = torch.zeros(256, 256, **bf)                    # another K
     a3, b3 = torch.zeros(256, 128, 2, **bf), torch.zeros(256, 128, 2, **bf)
     b_cpu = torch.zeros(256, 128, dtype=torch.bfloat16)
-    two = {"gemm_bt_8ph": ext.gemm_bt_8ph, "gemm_bt_256x32": ext.gemm_bt_256x32,
-           "gemm_bt_256sg": ext.gemm_bt_256sg, "gemm_bt": ext.gemm_bt,
+    two = {"gemm_bt": ext.gemm_bt,
            "gemm_bt_8ph_v": lambda x, y: ext.gemm_bt_8ph_v(x, y, 14)}
     for name, fn in two.items():
         for bad in ((a, b_wide), (a3, b), (a, b3), (a, b_cpu), (b_cpu, b)):
             with pytest.raises(RuntimeError):
                 fn(*bad)
         assert tuple(fn(a, b).shape) == (256, 256), name    # the well-formed call
-    for var in (-1, 10, 15, 25, 1000):                      # no such variant
+    for var in (-1, 0, 10, 13, 15, 18, 25, 1000):           # no such variant
         with pytest.raises(RuntimeError):
             ext.gemm_bt_8ph_v(a, b, var)
-    assert tuple(ext.gemm_bt_8ph_v(a, b, 0).shape) == (256, 256)
+    for var in (14, 21, 24):
+        assert tuple(ext.gemm_bt_8ph_v(a, b, var).shape) == (256, 256)
     # K below the two tiles the pipelined prologues need; K = 0
     a64, b64 = torch.zeros(256, 64, **bf), torch.zeros(256, 64, **bf)
     a0, b0 = torch.zeros(256, 0, **bf), torch.zeros(256, 0, **bf)
-    for fn in (ext.gemm_bt_8ph, two["gemm_bt_8ph_v"]):
-        for bad in ((a64, b64), (a0, b0)):
-            with pytest.raises(RuntimeError):
-                fn(*bad)
-    for fn in (ext.gemm_bt_256x32, ext.gemm_bt_256sg, ext.gemm_bt):
+    for bad in ((a64, b64), (a0, b0)):
         with pytest.raises(RuntimeError):
-            fn(a0, b0)
-        assert tuple(fn(a64, b64).shape) == (256, 256)
+            two["gemm_bt_8ph_v"](*bad)
+    with pytest.raises(RuntimeError):
+        ext.gemm_bt(a0, b0)
+    assert tuple(ext.gemm_bt(a64, b64).shape) == (256, 256)
     torch.cuda.synchronize()
