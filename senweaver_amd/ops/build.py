@@ -19,7 +19,7 @@ SOURCES = [
     os.path.join(CSRC, f)
     for f in ("bindings.hip", "elemwise.hip", "sampling.hip", "gemm.hip",
               "gemm_pipe.hip", "gemm_asm.hip", "attention.hip", "attention_v2.hip",
-              "attention_v4.hip", "gemm_lt.hip",
+              "attention_v5.hip", "gemm_lt.hip",
               "decode_attention.hip", "paged_prefill_attention.hip", "moe.hip",
               "fp8.hip")
 ]

@@ -432,11 +432,6 @@ torch::Tensor gemm_bt_mxfp8(torch::Tensor Aq, torch::Tensor As,
   auto C = torch::empty({M, N}, Aq.options().dtype(torch::kBFloat16));
   const int nwg256 = (M % 256 == 0 && N % 256 == 0) ? (M / 256) * (N / 256) : 0;
   if (nwg256 >= 160) {
-    // NOTE: a single-barrier pipeline port (gemm_bt_mxfp8_pipe_kernel, kept
-    // for reference) measured SLOWER (918-998 TF/s vs 1187-1325): the
-    // 32x32x64 f32x16 accumulators fragment the register budget at both
-    // 512-thr (72 B/lane spill) and 1024-thr (176 B/lane) geometries.
-    // Measured-and-documented rejection; see profiles/r02_gemm_pipeline.txt.
     gemm_bt_mxfp8_256_kernel<<<dim3(nwg256), dim3(512), 0, cur_stream()>>>(
         Aq.data_ptr<unsigned char>(), As.data_ptr<unsigned char>(),
         Bq.data_ptr<unsigned char>(), Bs.data_ptr<unsigned char>(),
@@ -532,9 +527,14 @@ torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   return o;
 }
 
-// v2: swapped-QK^T in-register-softmax kernel; returns O^T [B,H,D,S]
-torch::Tensor attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
-                          double scale) {
+// What the kernels that return O^T ask of their operands: D = 128, query
+// tiles of 128 rows, vt = V^T [B,Hk,D,S].
+struct AttnDims {
+  int B, H, Hk, S, D;
+};
+
+static AttnDims check_attn_ot(const torch::Tensor& q, const torch::Tensor& k,
+                              const torch::Tensor& vt, const char* op) {
   check_bf16(q, "q");
   check_bf16(k, "k");
   check_bf16(vt, "vt");
@@ -542,7 +542,14 @@ torch::Tensor attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   const int Hk = k.size(1);
   TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
   TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
-  check_attn_kv(k, vt, B, S, D, "attn_fwd_v2");
+  check_attn_kv(k, vt, B, S, D, op);
+  return {B, H, Hk, S, D};
+}
+
+// v2: swapped-QK^T in-register-softmax kernel; returns O^T [B,H,D,S]
+torch::Tensor attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
+                          double scale) {
+  const auto [B, H, Hk, S, D] = check_attn_ot(q, k, vt, "attn_fwd_v2");
   auto ot = torch::empty({B, H, D, S}, q.options());
   attn_fwd_v2_kernel<<<dim3(S / 128, H, B), dim3(256), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);
@@ -550,17 +557,11 @@ torch::Tensor attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   return ot;
 }
 
-// v3: v2 structure with 8 waves sharing one staged K/V tile (256 q rows)
+// v3: v2 structure with 8 waves sharing one staged K/V tile (256 q rows);
+// the ladder point v5 is measured against, not reached from ops
 torch::Tensor attn_fwd_v3(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
                           double scale) {
-  check_bf16(q, "q");
-  check_bf16(k, "k");
-  check_bf16(vt, "vt");
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hk = k.size(1);
-  TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
-  TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
-  check_attn_kv(k, vt, B, S, D, "attn_fwd_v3");
+  const auto [B, H, Hk, S, D] = check_attn_ot(q, k, vt, "attn_fwd_v3");
   auto ot = torch::empty({B, H, D, S}, q.options());
   attn_fwd_v3_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);
@@ -568,68 +569,15 @@ torch::Tensor attn_fwd_v3(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
   return ot;
 }
 
-// v4 probe family: v3 + {defer-max, async-STAGE register staging,
-// glds-after-QK} lever matrix (attention_v4.hip header for the map)
-#define DECL_V4(VAR)                                                         \
-  extern "C" __global__ void attn_fwd_v4_##VAR##_kernel(                     \
-      const ushort*, const ushort*, const ushort*, ushort*, int, int, int,   \
-      int, float);
-DECL_V4(0) DECL_V4(1) DECL_V4(2) DECL_V4(3)
-DECL_V4(4) DECL_V4(5) DECL_V4(6) DECL_V4(7)
-DECL_V4(8) DECL_V4(9) DECL_V4(10) DECL_V4(11) DECL_V4(12) DECL_V4(13) DECL_V4(14) DECL_V4(15) DECL_V4(16) DECL_V4(17) DECL_V4(18) DECL_V4(19)
-
-torch::Tensor attn_fwd_v4(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
-                          double scale, long var) {
-  check_bf16(q, "q");
-  check_bf16(k, "k");
-  check_bf16(vt, "vt");
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hk = k.size(1);
-  TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
-  TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
-  check_attn_kv(k, vt, B, S, D, "attn_fwd_v4");
-  auto ot = torch::empty({B, H, D, S}, q.options());
-  const bool four_wave = (var == 16 || var == 18);  // QBLK 128, 256 threads
-  dim3 grid(four_wave ? (S + 127) / 128 : (S + 255) / 256, H, B);
-  if (var == 19) {  // persistent: one block per CU walks the work items
-    const int NW = ((S + 255) / 256) * H * B;
-    grid = dim3(NW < 256 ? NW : 256, 1, 1);
-  }
-  const dim3 blk(four_wave ? 256 : 512);
-  auto s = cur_stream();
-#define LAUNCH_V4(VAR)                                                       \
-  case VAR:                                                                  \
-    attn_fwd_v4_##VAR##_kernel<<<grid, blk, 0, s>>>(                         \
-        bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S,  \
-        (float)scale);                                                       \
-    break;
-  switch (var) {
-    LAUNCH_V4(0) LAUNCH_V4(1) LAUNCH_V4(2) LAUNCH_V4(3)
-    LAUNCH_V4(4) LAUNCH_V4(5) LAUNCH_V4(6) LAUNCH_V4(7)
-    LAUNCH_V4(8) LAUNCH_V4(9) LAUNCH_V4(10) LAUNCH_V4(11) LAUNCH_V4(12) LAUNCH_V4(13) LAUNCH_V4(14) LAUNCH_V4(15) LAUNCH_V4(16) LAUNCH_V4(17) LAUNCH_V4(18) LAUNCH_V4(19)
-    default: TORCH_CHECK(false, "attn_fwd_v4: unknown variant ", var);
-  }
-#undef LAUNCH_V4
-  HIP_CHECK_KERNEL();
-  return ot;
-}
-
-// v5 = promoted winner of the v4 lever matrix (variant 15: register-staged
-// async prefetch, double LDS buffer, defer-max, softmax VALU diet, sm-split;
-// 501 TF @ B4 H32 S2048 / 580 TF @ B1 H32 S8192 causal vs v3's 434/477 —
-// profiles/r02_attn_ladder.txt)
+// v5, the production kernel (attention_v5.hip): 8 waves share a K/V tile
+// (256 q rows per block), register-staged prefetch into a double LDS buffer,
+// defer-max, softmax VALU diet, sm-split; 501 TF @ B4 H32 S2048 / 580 TF @ B1
+// H32 S8192 causal (profiles/r02_attn_ladder.txt).  Returns O^T [B,H,D,S].
 torch::Tensor attn_fwd_v5(torch::Tensor q, torch::Tensor k, torch::Tensor vt,
                           double scale) {
-  check_bf16(q, "q");
-  check_bf16(k, "k");
-  check_bf16(vt, "vt");
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hk = k.size(1);
-  TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
-  TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
-  check_attn_kv(k, vt, B, S, D, "attn_fwd_v5");
+  const auto [B, H, Hk, S, D] = check_attn_ot(q, k, vt, "attn_fwd_v5");
   auto ot = torch::empty({B, H, D, S}, q.options());
-  attn_fwd_v4_15_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
+  attn_fwd_v5_kernel<<<dim3((S + 255) / 256, H, B), dim3(512), 0, cur_stream()>>>(
       bf16_ptr(q), bf16_ptr(k), bf16_ptr(vt), bf16_mut(ot), B, H, Hk, S, (float)scale);
   HIP_CHECK_KERNEL();
   return ot;
@@ -708,15 +656,8 @@ static torch::Tensor attn_packed_launch(torch::Tensor q, torch::Tensor k,
                                         torch::Tensor skip, torch::Tensor base,
                                         int64_t Tp, bool row_major,
                                         c10::optional<torch::Tensor> out) {
-  check_bf16(q, "q");
-  check_bf16(k, "k");
-  check_bf16(vt, "vt");
   TORCH_CHECK(q.dim() == 4, "attn_fwd_v5_packed: q must be [B,H,S,D]");
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hk = k.size(1);
-  TORCH_CHECK(D == 128 && S % 128 == 0 && H % Hk == 0);
-  TORCH_CHECK(vt.size(1) == Hk && vt.size(2) == D && vt.size(3) == S);
-  check_attn_kv(k, vt, B, S, D, "attn_fwd_v5_packed");
+  const auto [B, H, Hk, S, D] = check_attn_ot(q, k, vt, "attn_fwd_v5_packed");
   TORCH_CHECK(Tp > 0 && Tp <= (int64_t)B * S && (int64_t)B * S < (1LL << 31),
               "attn_fwd_v5_packed: Tp must be in (0, B*S]");
   check_plan(skip, B, "skip");
@@ -998,8 +939,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, "causal flash attention fwd (D=128, GQA)");
   m.def("attn_fwd_v2", &attn_fwd_v2, "swapped-QK^T attention; O^T out [B,H,D,S]");
   m.def("attn_fwd_v3", &attn_fwd_v3, "v2 with 8-wave shared K/V tiles; O^T out");
-  m.def("attn_fwd_v4", &attn_fwd_v4, "v4 lever-matrix probe (variant arg)");
-  m.def("attn_fwd_v5", &attn_fwd_v5, "production attention (v4 winner); O^T out");
+  m.def("attn_fwd_v5", &attn_fwd_v5, "production attention; O^T out");
   m.def("rope_scatter_qkv_packed", &rope_scatter_qkv_packed,
         "rope_scatter_qkv reading prefix-packed qkv rows");
   m.def("vt_from_qkv_packed", &vt_from_qkv_packed,

@@ -134,7 +134,7 @@ SW_KERNEL gemm_bt_mxfp8_256_kernel(const unsigned char* A,
                                    const unsigned char* Bs, ushort* C, int M,
                                    int N, int K);
 
-// ---- attention.hip, attention_v2.hip, attention_v4.hip: prefill ----
+// ---- attention.hip, attention_v2.hip, attention_v5.hip: prefill ----
 SW_KERNEL attn_fwd_bf16_kernel(const ushort* Q, const ushort* K,
                                const ushort* VT, ushort* O, int B, int H,
                                int Hk, int S, float scale);
@@ -144,9 +144,9 @@ SW_KERNEL attn_fwd_v2_kernel(const ushort* Q, const ushort* K, const ushort* VT,
 SW_KERNEL attn_fwd_v3_kernel(const ushort* Q, const ushort* K, const ushort* VT,
                              ushort* OT, int B, int H, int Hk, int S,
                              float scale);
-SW_KERNEL attn_fwd_v4_15_kernel(const ushort* Q, const ushort* K,
-                                const ushort* VT, ushort* OT, int B, int H,
-                                int Hk, int S, float scale);
+SW_KERNEL attn_fwd_v5_kernel(const ushort* Q, const ushort* K, const ushort* VT,
+                             ushort* OT, int B, int H, int Hk, int S,
+                             float scale);
 SW_KERNEL attn_fwd_v5_packed_kernel(const ushort* Q, const ushort* K,
                                     const ushort* VT, ushort* OT, int B, int H,
                                     int Hk, int S, float scale, const int* skip,

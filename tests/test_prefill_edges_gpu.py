@@ -126,13 +126,12 @@ def _bindings():
         "attn_fwd": ext.attn_fwd,
         "attn_fwd_v2": ext.attn_fwd_v2,
         "attn_fwd_v3": ext.attn_fwd_v3,
-        "attn_fwd_v4": lambda q, k, vt, s: ext.attn_fwd_v4(q, k, vt, s, 15),
         "attn_fwd_v5": ext.attn_fwd_v5,
     }
 
 
 @pytest.mark.parametrize("name", ["attn_fwd", "attn_fwd_v2", "attn_fwd_v3",
-                                  "attn_fwd_v4", "attn_fwd_v5"])
+                                  "attn_fwd_v5"])
 def test_bindings_reject_mismatched_k_vt(dev, gen, name):
     """k's batch, sequence and head dimensions and vt's batch must match q.
     Only OVERSIZED operands are used, so a binding without the check would
