@@ -170,6 +170,55 @@ def bench_fp8():
               f" TF/s   (quant_mx {M * K * 2 / tq / 1e9:5.0f} GB/s)")
 
 
+def bench_tile():
+    """The six single-barrier tile GEMMs of gemm.hip / moe.hip / fp8.hip, each
+    at a shape whose dispatch reaches it (the asm / v14 kernels and the vendor
+    library take the other shapes).  Device time by events, 5 repeats each."""
+    dev = torch.device("cuda:0")
+    ext = ops.hip_ext()
+
+    def bf16(*shape):
+        return torch.randn(*shape, dtype=torch.bfloat16, device=dev)
+
+    def dense(M, N, K):
+        a, b = bf16(M, K), bf16(N, K)
+        return lambda: ext.gemm_bt(a, b)
+
+    def grouped(E, rows, N, K):
+        # the tile map ops.grouped_gemm_bt builds under SENWEAVER_GEMM=hip
+        a, w = bf16(E * rows, K), bf16(E, N, K)
+        m0 = list(range(0, E * rows, 128))
+        te = torch.tensor([m // rows for m in m0], dtype=torch.int32, device=dev)
+        tm = torch.tensor(m0, dtype=torch.int32, device=dev)
+        ends = torch.tensor([(e + 1) * rows for e in range(E)], dtype=torch.int32, device=dev)
+        return lambda: ext.grouped_gemm_bt(a, w, te, tm, ends)
+
+    def quant(M, N, K, q, gemm):
+        (aq, asc), (bq, bsc) = q(bf16(M, K)), q(bf16(N, K))
+        return lambda: gemm(aq, asc, bq, bsc)
+
+    cases = [
+        ("gemm_bt_bf16_kernel", (2048, 4096, 4096), dense),          # 128 256-tiles < 160
+        ("gemm_bt_bf16_256_kernel", (4096, 4096, 4160), dense),      # K % 128 == 64
+        ("grouped_gemm_bt_bf16_kernel", (8 * 1024, 14336, 4096),
+         lambda M, N, K: grouped(8, 1024, N, K)),
+        ("gemm_bt_fp8_kernel", (4096, 4096, 4096),
+         lambda M, N, K: quant(M, N, K, ext.quant_fp8, ext.gemm_bt_fp8)),
+        ("gemm_bt_mxfp8_kernel", (2048, 4096, 4096),
+         lambda M, N, K: quant(M, N, K, ext.quant_mxfp8, ext.gemm_bt_mxfp8)),
+        ("gemm_bt_mxfp8_256_kernel", (8192, 8192, 8192),
+         lambda M, N, K: quant(M, N, K, ext.quant_mxfp8, ext.gemm_bt_mxfp8)),
+    ]
+    for name, (M, N, K), make in cases:
+        fn = make(M, N, K)
+        us = sorted(event_us(lambda i: fn(), 1, warmup=5, iters=20) for _ in range(5))
+        fl = 2.0 * M * N * K
+        print(f"TILE {name:28s} {M}x{N}x{K}: median {us[2]:8.1f} us  "
+              f"{fl / us[2] / 1e6:7.1f} TF/s  (runs: {' '.join(f'{u:.1f}' for u in us)})")
+        del fn
+        torch.cuda.empty_cache()
+
+
 def bench_attn():
     dev = torch.device("cuda:0")
     for (B, H, Hk, S) in [(4, 32, 8, 2048), (2, 32, 8, 4096), (1, 32, 8, 8192)]:
@@ -242,6 +291,8 @@ if __name__ == "__main__":
         bench_gemm8()
     if which in ("all", "fp8"):
         bench_fp8()
+    if which == "tile":
+        bench_tile()
     if which in ("all", "attn"):
         bench_attn()
     if which in ("all", "gemv"):

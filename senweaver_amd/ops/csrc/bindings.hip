@@ -55,6 +55,22 @@ GemmDims check_gemm_256(const torch::Tensor& a, const torch::Tensor& b,
   return d;
 }
 
+// Decode GEMV M-bucket.  The GEMV kernels are instantiated for 1 / 2 / 4 / 8
+// (/ 16) activation rows and read that many rows unconditionally: MM is the
+// bucket M rounds up to, pad() the activation zero-padded to MM rows.
+struct MBucket {
+  int MM = 1;
+  MBucket(int M, int max_bucket) {
+    while (MM < M && MM < max_bucket) MM *= 2;
+  }
+  torch::Tensor pad(const torch::Tensor& x) const {
+    if (x.size(0) >= MM) return x;
+    auto xp = torch::zeros({(long)MM, x.size(1)}, x.options());
+    xp.narrow(0, 0, x.size(0)).copy_(x);
+    return xp;
+  }
+};
+
 // rmsnorm / fused_add_rmsnorm: the kernel reads hidden / 8 16-byte vectors
 // of every row of x and of w.  Returns hidden.
 int check_norm_operands(const torch::Tensor& x, const torch::Tensor& w, const char* op) {
@@ -251,12 +267,9 @@ torch::Tensor gemm_bt(torch::Tensor A, torch::Tensor B) {
     TORCH_CHECK(N % 4 == 0 && K >= 512 && K % 512 == 0,
                 "gemv path needs N%4==0, K%512==0 (K >= 512)");
     // wave-per-row coalesced GEMV; A must be padded to the MM bucket rows
-    int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
-    torch::Tensor Ap = A;
-    if (A.size(0) < MM) {
-      Ap = torch::zeros({MM, (long)K}, A.options());
-      Ap.narrow(0, 0, M).copy_(A);
-    }
+    const MBucket bucket(M, 16);
+    const int MM = bucket.MM;
+    const torch::Tensor Ap = bucket.pad(A);
     const dim3 grid((N + 3) / 4);
     auto launch = [&](auto kern) {
       kern<<<grid, dim3(256), 0, cur_stream()>>>(bf16_ptr(Ap), bf16_ptr(B),
@@ -462,23 +475,16 @@ std::vector<torch::Tensor> gemv_norm_bt(torch::Tensor x, c10::optional<torch::Te
               "gemv_norm_bt: res_in must be [M, K]");
   auto C = torch::empty({M, N}, x.options());
   auto res_out = torch::empty({M, K}, x.options());
-  int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
-  torch::Tensor xp = x, rp;
+  const MBucket bucket(M, 16);
+  const int MM = bucket.MM;
+  const torch::Tensor xp = bucket.pad(x);
+  torch::Tensor rp;
   const ushort* rptr = nullptr;
   if (res_in.has_value()) {
     check_bf16(*res_in, "res_in");
-    rp = *res_in;
+    rp = bucket.pad(*res_in);
+    rptr = bf16_ptr(rp);
   }
-  if (M < MM) {
-    xp = torch::zeros({MM, (long)K}, x.options());
-    xp.narrow(0, 0, M).copy_(x);
-    if (res_in.has_value()) {
-      auto r2 = torch::zeros({MM, (long)K}, x.options());
-      r2.narrow(0, 0, M).copy_(rp);
-      rp = r2;
-    }
-  }
-  if (res_in.has_value()) rptr = bf16_ptr(rp);
   const dim3 grid((N + 3) / 4);
   auto launch = [&](auto kern) {
     kern<<<grid, dim3(256), 0, cur_stream()>>>(bf16_ptr(xp), rptr,
@@ -854,12 +860,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(M >= 1 && M <= 8 && K >= 1024 && K % 1024 == 0 && bq.size(1) == K &&
                 N % 4 == 0 && bs.numel() == N);
     TORCH_CHECK(bq.is_contiguous() && bs.is_contiguous());
-    const int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
-    torch::Tensor xp = x;
-    if (M < MM) {
-      xp = torch::zeros({MM, (long)K}, x.options());
-      xp.narrow(0, 0, M).copy_(x);
-    }
+    const MBucket bucket(M, 8);
+    const int MM = bucket.MM;
+    const torch::Tensor xp = bucket.pad(x);
     auto C = torch::empty({M, N}, x.options());
     // MM==1 runs 1 row/wave (grid N/4); MM>1 runs 2 rows/wave (N/8)
     const int nb = MM > 1 ? (N + 7) / 8 : (N + 3) / 4;
@@ -884,12 +887,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(M >= 1 && M <= 8 && K >= 1024 && K % 1024 == 0 && bq.size(1) == K &&
                 bs.dim() == 2 && bs.size(0) == N && bs.size(1) == K / 32 && N % 4 == 0);
     TORCH_CHECK(bq.is_contiguous() && bs.is_contiguous());
-    const int MM = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
-    torch::Tensor xp = x;
-    if (M < MM) {
-      xp = torch::zeros({MM, (long)K}, x.options());
-      xp.narrow(0, 0, M).copy_(x);
-    }
+    const MBucket bucket(M, 8);
+    const int MM = bucket.MM;
+    const torch::Tensor xp = bucket.pad(x);
     auto C = torch::empty({M, N}, x.options());
     auto launch = [&](auto kern) {
       kern<<<dim3(N / 4), dim3(256), 0, cur_stream()>>>(

@@ -14,8 +14,7 @@
 
 #include "common.h"
 #include "kernels.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "tile_gemm.h"
 
 #define FBK 128  // fp8 K-tile depth (bytes == elements)
 
@@ -58,42 +57,12 @@ quant_fp8_rowwise_kernel(const ushort* __restrict__ x, unsigned char* __restrict
 // fp8 GEMM: C[M,N] = (A_q[M,K] @ B_q[N,K]^T) * a_s[m] * b_s[n], bf16 out.
 // 128x128 tile, 4 waves (2x2), glds double buffer, one barrier per K-tile.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void stage_fp8_tile(
-    const unsigned char* __restrict__ src, long long ldK, unsigned char* lds_tile,
-    int tid) {
-  // 128 rows x 8 chunks(16B=16 fp8) = 1024 chunks / 256 threads = 4 glds
-  const int wave_chunk = tid & ~63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s = i * 256 + tid;
-    const int row = s >> 3;
-    const int c = (s & 7) ^ (row & 7);
-    const unsigned char* g = src + (long long)row * ldK + c * 16;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds_tile + (long long)(i * 256 + wave_chunk) * 16),
-        16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ long read_fp8_frag(const unsigned char* lds_tile, int row,
-                                              int byte_off) {
-  const int c = byte_off >> 4;
-  const int phys = (c ^ (row & 7)) * 16 + (byte_off & 15);
-  return *reinterpret_cast<const long*>(lds_tile + row * FBK + phys);
-}
-
 extern "C" __global__ void __launch_bounds__(256, 2)
 gemm_bt_fp8_kernel(const unsigned char* __restrict__ A, const float* __restrict__ a_s,
                    const unsigned char* __restrict__ B, const float* __restrict__ b_s,
                    ushort* __restrict__ C, int M, int N, int K) {
   const int nwg = (M / 128) * (N / 128);
-  int wgid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wgid % 8, pos = wgid / 8;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int wgid = xcd_remap(blockIdx.x, nwg);
   const int tiles_n = N / 128;
   const int tile_m = wgid / tiles_n;
   const int tile_n = wgid % tiles_n;
@@ -121,15 +90,15 @@ gemm_bt_fp8_kernel(const unsigned char* __restrict__ A, const float* __restrict_
   const int frag_kgrp = lane >> 4;
 
   const int ntiles = K / FBK;
-  stage_fp8_tile(Atile, K, lds[0][0], tid);
-  stage_fp8_tile(Btile, K, lds[0][1], tid);
+  stage_tile_glds<256>(Atile, K, lds[0][0], tid);
+  stage_tile_glds<256>(Btile, K, lds[0][1], tid);
   __syncthreads();
 
   int buf = 0;
   for (int t = 0; t < ntiles; ++t) {
     if (t + 1 < ntiles) {
-      stage_fp8_tile(Atile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][0], tid);
-      stage_fp8_tile(Btile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][1], tid);
+      stage_tile_glds<256>(Atile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][0], tid);
+      stage_tile_glds<256>(Btile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][1], tid);
     }
     const unsigned char* Al = lds[buf][0];
     const unsigned char* Bl = lds[buf][1];
@@ -182,8 +151,6 @@ gemm_bt_fp8_kernel(const unsigned char* __restrict__ A, const float* __restrict_
 // scale exponent = floor(log2(amax)) - 8 (e4m3 emax), elements saturate at
 // +-448.
 // ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // bf16 [rows, K] -> fp8 q[rows, K] + e8m0 scales [rows, K/32]
 extern "C" __global__ void __launch_bounds__(256)
@@ -229,101 +196,90 @@ quant_mxfp8_kernel(const ushort* __restrict__ x, unsigned char* __restrict__ q,
 }
 
 // C[M,N] = dequant(A_q, A_s) @ dequant(B_q, B_s)^T, bf16 out.
-// 128x128 tile, BK=128 fp8 bytes, 4 waves (2x2, 64x64 per wave = 2x2 frags
-// of 32x32), glds double buffer + one __syncthreads per K-tile.
+// TILE x TILE tile, BK=128 fp8 bytes, glds double buffer + one
+// __syncthreads per K-tile.  TILE = 128: 4 waves (2x2), 64x64 per wave =
+// 2x2 frags of 32x32.  TILE = 256: 8 waves (2 m x 4 n), 128x64 per wave =
+// 4x2 frags.
 //
 // Fragment layout (probed empirically, benchmarks/probe_mx.py): per 64-k
 // instruction, lane half lhi holds k in [lhi*16, lhi*16+16) u
 // [32+lhi*16, 32+lhi*16+16) — 16 bytes from EACH of the two 32-element
 // scale blocks — while the per-lane scale register of half lhi supplies
 // the e8m0 scale for block lhi.  So the two 16-B chunks a lane reads are
-// (kk*4 + lhi) and (kk*4 + lhi + 2), and the scale byte is block
-// (t*4 + kk*2 + lhi) of that fragment's row.
-__device__ __forceinline__ i32x8 read_mx_frag(const unsigned char* lds_tile,
-                                              int row, int c0) {
-  // two 16-B chunks (c0, c0+2) — one from each scale block — XOR-swizzled
-  i32x8 out;
-  const int p0 = (c0 ^ (row & 7)) * 16;
-  const int p1 = ((c0 + 2) ^ (row & 7)) * 16;
-  *reinterpret_cast<int4*>(&out) = *reinterpret_cast<const int4*>(lds_tile + row * FBK + p0);
-  *(reinterpret_cast<int4*>(&out) + 1) = *reinterpret_cast<const int4*>(lds_tile + row * FBK + p1);
-  return out;
-}
+// (kk*4 + lhi) and (kk*4 + lhi + 2) (read_mx_frag in tile_gemm.h), and the
+// scale byte is block (t*4 + kk*2 + lhi) of that fragment's row.
+template <int TILE>
+static __device__ __forceinline__ void gemm_bt_mxfp8_body(
+    const unsigned char* __restrict__ A, const unsigned char* __restrict__ As,
+    const unsigned char* __restrict__ B, const unsigned char* __restrict__ Bs,
+    ushort* __restrict__ C, int M, int N, int K) {
+  constexpr int THREADS = 2 * TILE;
+  constexpr int MI = TILE / 64;  // 32-row m-fragments per wave
+  constexpr int WN = TILE / 64;  // waves along n (2 along m)
 
-extern "C" __global__ void __launch_bounds__(256, 2)
-gemm_bt_mxfp8_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ As,
-                     const unsigned char* __restrict__ B, const unsigned char* __restrict__ Bs,
-                     ushort* __restrict__ C, int M, int N, int K) {
-  const int nwg = (M / 128) * (N / 128);
-  int wgid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wgid % 8, pos = wgid / 8;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int tiles_n = N / 128;
+  const int nwg = (M / TILE) * (N / TILE);
+  const int wgid = xcd_remap(blockIdx.x, nwg);
+  const int tiles_n = N / TILE;
   const int tile_m = wgid / tiles_n;
   const int tile_n = wgid % tiles_n;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int wm = wid >> 1;
-  const int wn = wid & 1;
+  const int wm = wid / WN;
+  const int wn = wid % WN;
   const int l31 = lane & 31;
   const int lhi = lane >> 5;
 
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][128 * FBK];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][TILE * FBK];
 
-  const unsigned char* Atile = A + (long long)tile_m * 128 * K;
-  const unsigned char* Btile = B + (long long)tile_n * 128 * K;
+  const unsigned char* Atile = A + (long long)tile_m * TILE * K;
+  const unsigned char* Btile = B + (long long)tile_n * TILE * K;
   const int sld = K / 32;  // scale row stride
-  const unsigned char* Astile = As + (long long)tile_m * 128 * sld;
-  const unsigned char* Bstile = Bs + (long long)tile_n * 128 * sld;
 
-  f32x16 acc[2][2];
+  f32x16 acc[MI][2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int m_base = wm * 64;
+  const int m_base = wm * (TILE / 2);
   const int n_base = wn * 64;
-
-  const int ntiles = K / FBK;
-  stage_fp8_tile(Atile, K, lds[0][0], tid);
-  stage_fp8_tile(Btile, K, lds[0][1], tid);
 
   // scale rows this lane's fragments use (dword = the 4 e8m0 bytes of one
   // 128-deep K-tile); prefetched one tile ahead so the byte extracts in the
   // MFMA loop never wait on global memory
-  const unsigned char* As_row[2] = {
-      Astile + (long long)(m_base + 0 * 32 + l31) * sld,
-      Astile + (long long)(m_base + 1 * 32 + l31) * sld};
-  const unsigned char* Bs_row[2] = {
-      Bstile + (long long)(n_base + 0 * 32 + l31) * sld,
-      Bstile + (long long)(n_base + 1 * 32 + l31) * sld};
-  unsigned sa_dw[2], sb_dw[2];
+  const unsigned char* As_row[MI];
+  const unsigned char* Bs_row[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    sa_dw[i] = *reinterpret_cast<const unsigned*>(As_row[i]);
-    sb_dw[i] = *reinterpret_cast<const unsigned*>(Bs_row[i]);
-  }
+  for (int i = 0; i < MI; ++i)
+    As_row[i] = As + ((long long)tile_m * TILE + m_base + i * 32 + l31) * sld;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    Bs_row[i] = Bs + ((long long)tile_n * TILE + n_base + i * 32 + l31) * sld;
+  unsigned sa_dw[MI], sb_dw[2];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) sa_dw[i] = *reinterpret_cast<const unsigned*>(As_row[i]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) sb_dw[i] = *reinterpret_cast<const unsigned*>(Bs_row[i]);
+
+  const int ntiles = K / FBK;
+  stage_tile_glds<THREADS>(Atile, K, lds[0][0], tid);
+  stage_tile_glds<THREADS>(Btile, K, lds[0][1], tid);
   __syncthreads();
 
   int buf = 0;
   for (int t = 0; t < ntiles; ++t) {
-    unsigned na[2], nb[2];
+    unsigned na[MI], nb[2];
     if (t + 1 < ntiles) {
-      stage_fp8_tile(Atile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][0], tid);
-      stage_fp8_tile(Btile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][1], tid);
+      stage_tile_glds<THREADS>(Atile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][0], tid);
+      stage_tile_glds<THREADS>(Btile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][1], tid);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        na[i] = *reinterpret_cast<const unsigned*>(As_row[i] + (t + 1) * 4);
-        nb[i] = *reinterpret_cast<const unsigned*>(Bs_row[i] + (t + 1) * 4);
-      }
+      for (int i = 0; i < MI; ++i) na[i] = *reinterpret_cast<const unsigned*>(As_row[i] + (t + 1) * 4);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) nb[i] = *reinterpret_cast<const unsigned*>(Bs_row[i] + (t + 1) * 4);
     }
     const unsigned char* Al = lds[buf][0];
     const unsigned char* Bl = lds[buf][1];
@@ -332,156 +288,15 @@ gemm_bt_mxfp8_kernel(const unsigned char* __restrict__ A, const unsigned char* _
     for (int kk = 0; kk < 2; ++kk) {  // FBK=128 in 2 MFMA steps of K=64
       // lane half lhi supplies the scale of block (kk*2 + lhi) of this tile
       const int sh = 8 * (kk * 2 + lhi);
-      i32x8 af[2], bf[2];
-      int sa[2], sb[2];
+      i32x8 af[MI], bf[2];
 #pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        af[mi] = read_mx_frag(Al, m_base + mi * 32 + l31, kk * 4 + lhi);
-        sa[mi] = (sa_dw[mi] >> sh) & 0xff;
-      }
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        bf[ni] = read_mx_frag(Bl, n_base + ni * 32 + l31, kk * 4 + lhi);
-        sb[ni] = (sb_dw[ni] >> sh) & 0xff;
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0, sa[mi], 0, sb[ni]);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();
-    buf ^= 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { sa_dw[i] = na[i]; sb_dw[i] = nb[i]; }
-  }
-
-  // C/D 32x32 map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
-  const long long c_col0 = (long long)tile_n * 128 + n_base + l31;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const long long row = (long long)tile_m * 128 + m_base + mi * 32
-                            + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-      ushort* crow = C + row * N;
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        crow[c_col0 + ni * 32] = f2bf(acc[mi][ni][r]);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// 256x256-tile MX fp8 GEMM: 8 waves (2 m x 4 n), wave tile 128x64 as 4x2
-// frags of 32x32.  Raises the MFMA:ds_read ratio from 8:4 to 8:6-per-
-// double-the-work (6 frag reads feed 8 scaled MFMAs vs 4 feeding 4) and
-// halves barriers per flop; 1 block/CU (acc alone is 128 VGPRs).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void stage_fp8_tile_256(
-    const unsigned char* __restrict__ src, long long ldK, unsigned char* lds_tile,
-    int tid) {
-  // 256 rows x 8 chunks(16B) = 2048 chunks / 512 threads = 4 glds each
-  const int wave_chunk = tid & ~63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s = i * 512 + tid;
-    const int row = s >> 3;
-    const int c = (s & 7) ^ (row & 7);
-    const unsigned char* g = src + (long long)row * ldK + c * 16;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds_tile + (long long)(i * 512 + wave_chunk) * 16),
-        16, 0, 0);
-  }
-}
-
-extern "C" __global__ void __launch_bounds__(512, 1)
-gemm_bt_mxfp8_256_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ As,
-                         const unsigned char* __restrict__ B, const unsigned char* __restrict__ Bs,
-                         ushort* __restrict__ C, int M, int N, int K) {
-  const int nwg = (M / 256) * (N / 256);
-  int wgid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wgid % 8, pos = wgid / 8;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int tiles_n = N / 256;
-  const int tile_m = wgid / tiles_n;
-  const int tile_n = wgid % tiles_n;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = wid >> 2;      // 0..1 -> 128-row half
-  const int wn = wid & 3;       // 0..3 -> 64-col quarter
-  const int l31 = lane & 31;
-  const int lhi = lane >> 5;
-
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][256 * FBK];
-
-  const unsigned char* Atile = A + (long long)tile_m * 256 * K;
-  const unsigned char* Btile = B + (long long)tile_n * 256 * K;
-  const int sld = K / 32;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int m_base = wm * 128;
-  const int n_base = wn * 64;
-
-  const unsigned char* As_row[4];
-  const unsigned char* Bs_row[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    As_row[i] = As + ((long long)tile_m * 256 + m_base + i * 32 + l31) * sld;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-    Bs_row[i] = Bs + ((long long)tile_n * 256 + n_base + i * 32 + l31) * sld;
-  unsigned sa_dw[4], sb_dw[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) sa_dw[i] = *reinterpret_cast<const unsigned*>(As_row[i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) sb_dw[i] = *reinterpret_cast<const unsigned*>(Bs_row[i]);
-
-  const int ntiles = K / FBK;
-  stage_fp8_tile_256(Atile, K, lds[0][0], tid);
-  stage_fp8_tile_256(Btile, K, lds[0][1], tid);
-  __syncthreads();
-
-  int buf = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    unsigned na[4], nb[2];
-    if (t + 1 < ntiles) {
-      stage_fp8_tile_256(Atile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][0], tid);
-      stage_fp8_tile_256(Btile + (long long)(t + 1) * FBK, K, lds[buf ^ 1][1], tid);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) na[i] = *reinterpret_cast<const unsigned*>(As_row[i] + (t + 1) * 4);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) nb[i] = *reinterpret_cast<const unsigned*>(Bs_row[i] + (t + 1) * 4);
-    }
-    const unsigned char* Al = lds[buf][0];
-    const unsigned char* Bl = lds[buf][1];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int sh = 8 * (kk * 2 + lhi);
-      i32x8 af[4], bf[2];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+      for (int mi = 0; mi < MI; ++mi)
         af[mi] = read_mx_frag(Al, m_base + mi * 32 + l31, kk * 4 + lhi);
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
         bf[ni] = read_mx_frag(Bl, n_base + ni * 32 + l31, kk * 4 + lhi);
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+      for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
@@ -492,21 +307,39 @@ gemm_bt_mxfp8_256_kernel(const unsigned char* __restrict__ A, const unsigned cha
     __syncthreads();
     buf ^= 1;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) sa_dw[i] = na[i];
+    for (int i = 0; i < MI; ++i) sa_dw[i] = na[i];
 #pragma unroll
     for (int i = 0; i < 2; ++i) sb_dw[i] = nb[i];
   }
 
-  const long long c_col0 = (long long)tile_n * 256 + n_base + l31;
+  // C/D 32x32 map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
+  const long long c_col0 = (long long)tile_n * TILE + n_base + l31;
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
+  for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const long long row = (long long)tile_m * 256 + m_base + mi * 32
+      const long long row = (long long)tile_m * TILE + m_base + mi * 32
                             + (r & 3) + 8 * (r >> 2) + 4 * lhi;
       ushort* crow = C + row * N;
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
         crow[c_col0 + ni * 32] = f2bf(acc[mi][ni][r]);
     }
+}
+
+extern "C" __global__ void __launch_bounds__(256, 2)
+gemm_bt_mxfp8_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ As,
+                     const unsigned char* __restrict__ B, const unsigned char* __restrict__ Bs,
+                     ushort* __restrict__ C, int M, int N, int K) {
+  gemm_bt_mxfp8_body<128>(A, As, B, Bs, C, M, N, K);
+}
+
+// 256x256 tile: raises the MFMA:ds_read ratio from 8:4 to 8:6-per-
+// double-the-work (6 frag reads feed 8 scaled MFMAs vs 4 feeding 4) and
+// halves barriers per flop; 1 block/CU (acc alone is 128 VGPRs).
+extern "C" __global__ void __launch_bounds__(512, 1)
+gemm_bt_mxfp8_256_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ As,
+                         const unsigned char* __restrict__ B, const unsigned char* __restrict__ Bs,
+                         ushort* __restrict__ C, int M, int N, int K) {
+  gemm_bt_mxfp8_body<256>(A, As, B, Bs, C, M, N, K);
 }

@@ -18,139 +18,34 @@
 //
 // f32 accumulation in AGPRs; bf16 output.  M,N % 128 == 0, K % 64 == 0
 // (host wrapper pads M; Llama-3 dims satisfy N,K natively).
+//
+// The pipeline itself (staging, swizzled reads, K loop, epilogue) is
+// gemm_bt_bf16_body in tile_gemm.h, shared with the grouped GEMM of moe.hip.
 
 #include "common.h"
 #include "kernels.h"
+#include "tile_gemm.h"
 
-typedef __attribute__((ext_vector_type(8))) short short8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define BM 128
-#define BN 128
-#define BK 64
-#define WARPS 4
-
-// chunk = 16 bytes = 8 bf16.  A row of BK=64 bf16 is 8 chunks.
-#define ROW_CHUNKS 8
-
-__device__ __forceinline__ void stage_tile_glds(
-    const ushort* __restrict__ src,  // tile origin: &X[row0*K + k0]
-    long long ldK,                   // leading dimension (elements)
-    ushort* lds_tile,                // 128*64 bf16, lane-linear destination
-    int tid) {
-  // 128 rows x 8 chunks = 1024 chunks; 256 threads -> 4 glds each.
-  // Linear slot s holds global chunk (row = s/8, c = (s%8) ^ (row&7)):
-  // inverse-swizzled source + swizzled read = same involution (rule 21).
-  // glds lane destination = wave-uniform base + lane*16, so the base must
-  // include this wave's 64-chunk sub-block, not just the iteration offset.
-  const int wave_chunk = tid & ~63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s = i * 256 + tid;
-    const int row = s >> 3;
-    const int c = (s & 7) ^ (row & 7);
-    const ushort* g = src + (long long)row * ldK + c * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds_tile + (long long)(i * 256 + wave_chunk) * 8),
-        16, 0, 0);
-  }
-}
-
-// ds_read_b128 of logical (row, chunk c) from a swizzled tile
-__device__ __forceinline__ short8 read_frag(const ushort* lds_tile, int row, int c) {
-  const int slot = row * ROW_CHUNKS + (c ^ (row & 7));
-  return *reinterpret_cast<const short8*>(lds_tile + slot * 8);
+// dense tile: XCD remap of the flat block id, then the shared body
+template <int TILE>
+static __device__ __forceinline__ void gemm_bt_bf16_dense(
+    const ushort* __restrict__ A, const ushort* __restrict__ B,
+    ushort* __restrict__ C, int M, int N, int K) {
+  const int nwg = (M / TILE) * (N / TILE);
+  const int wgid = xcd_remap(blockIdx.x, nwg);
+  const int tiles_n = N / TILE;
+  const int tile_m = wgid / tiles_n;
+  const int tile_n = wgid % tiles_n;
+  gemm_bt_bf16_body<TILE, false>(A + (long long)tile_m * TILE * K,
+                                 B + (long long)tile_n * TILE * K, C,
+                                 (long long)tile_m * TILE, (long long)tile_n * TILE,
+                                 N, K, 0);
 }
 
 extern "C" __global__ void __launch_bounds__(256, 2)
 gemm_bt_bf16_kernel(const ushort* __restrict__ A, const ushort* __restrict__ B,
                     ushort* __restrict__ C, int M, int N, int K) {
-  // ---- XCD-aware bijective remap of the flat workgroup id (T1) ----
-  const int nwg = (M / BM) * (N / BN);
-  int wgid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wgid % 8, pos = wgid / 8;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int tiles_n = N / BN;
-  const int tile_m = wgid / tiles_n;
-  const int tile_n = wgid % tiles_n;
-
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;      // wave 0..3
-  const int lane = tid & 63;
-  const int wm = wid >> 1;       // 2x2 wave grid: quadrant row
-  const int wn = wid & 1;        // quadrant col
-
-  __shared__ __attribute__((aligned(16))) ushort lds[2][2][BM * BK];  // [buf][A/B]
-
-  const ushort* Atile = A + (long long)tile_m * BM * K;
-  const ushort* Btile = B + (long long)tile_n * BN * K;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  const int m_base = wm * 64;  // within tile
-  const int n_base = wn * 64;
-  const int frag_row = lane & 15;      // m or n within 16
-  const int frag_kgrp = lane >> 4;     // k-group 0..3 (8 bf16 each)
-
-  const int ntiles = K / BK;
-  // Prologue: stage tile 0 into buffer 0
-  stage_tile_glds(Atile, K, lds[0][0], tid);
-  stage_tile_glds(Btile, K, lds[0][1], tid);
-  __syncthreads();
-
-  int buf = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    if (t + 1 < ntiles) {
-      stage_tile_glds(Atile + (long long)(t + 1) * BK, K, lds[buf ^ 1][0], tid);
-      stage_tile_glds(Btile + (long long)(t + 1) * BK, K, lds[buf ^ 1][1], tid);
-    }
-    const ushort* Al = lds[buf][0];
-    const ushort* Bl = lds[buf][1];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {  // two K=32 MFMA steps per BK=64
-      short8 af[4], bf[4];
-      const int c = kk * 4 + frag_kgrp;  // logical chunk of this lane's 8 bf16
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        af[mi] = read_frag(Al, m_base + mi * 16 + frag_row, c);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        bf[ni] = read_frag(Bl, n_base + ni * 16 + frag_row, c);
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // drains the in-flight glds (vmcnt 0) + barrier
-    buf ^= 1;
-  }
-
-  // ---- Epilogue: C[m][n], C-fragment map row=(lane>>4)*4+e, col=lane&15 ----
-  const long long c_row0 = (long long)tile_m * BM + m_base + (lane >> 4) * 4;
-  const long long c_col0 = (long long)tile_n * BN + n_base + (lane & 15);
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const long long row = c_row0 + mi * 16 + e;
-      ushort* crow = C + row * N;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        crow[c_col0 + ni * 16] = f2bf(acc[mi][ni][e]);
-    }
-  }
+  gemm_bt_bf16_dense<128>(A, B, C, M, N, K);
 }
 
 // ---------------------------------------------------------------------------
@@ -159,108 +54,10 @@ gemm_bt_bf16_kernel(const ushort* __restrict__ A, const ushort* __restrict__ B,
 // (1 block/CU), glds double-buffer, ONE __syncthreads per K-step.  Measured
 // class: ~1.15-1.22 PF/s bf16 at 4-8k shapes (vs ~0.9 for the 128^2 tile).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void stage_tile_glds_512(
-    const ushort* __restrict__ src, long long ldK, ushort* lds_tile, int tid) {
-  // 256 rows x 8 chunks = 2048 chunks staged by 512 threads -> 4 glds each
-  const int wave_chunk = tid & ~63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s = i * 512 + tid;
-    const int row = s >> 3;
-    const int c = (s & 7) ^ (row & 7);
-    const ushort* g = src + (long long)row * ldK + c * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds_tile + (long long)(i * 512 + wave_chunk) * 8),
-        16, 0, 0);
-  }
-}
-
 extern "C" __global__ void __launch_bounds__(512, 1)
 gemm_bt_bf16_256_kernel(const ushort* __restrict__ A, const ushort* __restrict__ B,
                         ushort* __restrict__ C, int M, int N, int K) {
-  const int nwg = (M / 256) * (N / 256);
-  int wgid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wgid % 8, pos = wgid / 8;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int tiles_n = N / 256;
-  const int tile_m = wgid / tiles_n;
-  const int tile_n = wgid % tiles_n;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = wid >> 2;  // 0..1
-  const int wn = wid & 3;   // 0..3
-
-  __shared__ __attribute__((aligned(16))) ushort lds[2][2][256 * 64];
-
-  const ushort* Atile = A + (long long)tile_m * 256 * K;
-  const ushort* Btile = B + (long long)tile_n * 256 * K;
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  const int m_base = wm * 128;
-  const int n_base = wn * 64;
-  const int frag_row = lane & 15;
-  const int frag_kgrp = lane >> 4;
-
-  const int ntiles = K / BK;
-  stage_tile_glds_512(Atile, K, lds[0][0], tid);
-  stage_tile_glds_512(Btile, K, lds[0][1], tid);
-  __syncthreads();
-
-  int buf = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    if (t + 1 < ntiles) {
-      stage_tile_glds_512(Atile + (long long)(t + 1) * BK, K, lds[buf ^ 1][0], tid);
-      stage_tile_glds_512(Btile + (long long)(t + 1) * BK, K, lds[buf ^ 1][1], tid);
-    }
-    const ushort* Al = lds[buf][0];
-    const ushort* Bl = lds[buf][1];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      short8 af[8], bf[4];
-      const int c = kk * 4 + frag_kgrp;
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi)
-        af[mi] = read_frag(Al, m_base + mi * 16 + frag_row, c);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        bf[ni] = read_frag(Bl, n_base + ni * 16 + frag_row, c);
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  const long long c_row0 = (long long)tile_m * 256 + m_base + (lane >> 4) * 4;
-  const long long c_col0 = (long long)tile_n * 256 + n_base + (lane & 15);
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const long long row = c_row0 + mi * 16 + e;
-      ushort* crow = C + row * N;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        crow[c_col0 + ni * 16] = f2bf(acc[mi][ni][e]);
-    }
-  }
+  gemm_bt_bf16_dense<256>(A, B, C, M, N, K);
 }
 
 // ---------------------------------------------------------------------------
@@ -270,43 +67,53 @@ gemm_bt_bf16_256_kernel(const ushort* __restrict__ A, const ushort* __restrict__
 // per (m, n) at the end.  N/4 blocks fill the chip without split-K, so the
 // partial-reduce pass is gone too.  A (M x K, <=128 KiB) streams from L2.
 // ---------------------------------------------------------------------------
+template <int MM>
+static __device__ __forceinline__ void gemv2_body(
+    const ushort* A, const ushort* B, ushort* C, int M, int N, int K) {
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + wid;
+  if (n >= N) return;
+  const ushort* brow = B + (long long)n * K;
+  float acc[MM];
+#pragma unroll
+  for (int m = 0; m < MM; ++m) acc[m] = 0.f;
+  // 2-deep software pipeline: the runtime-K loop otherwise keeps ONE
+  // weight load in flight per lane (latency-bound on the small rows)
+  short8 cur_ = __builtin_nontemporal_load(
+      reinterpret_cast<const short8*>(brow + lane * 8));
+  for (int k = lane * 8; k < K; k += 64 * 8) {
+    short8 nxt_;
+    if (k + 64 * 8 < K)
+      nxt_ = __builtin_nontemporal_load(
+          reinterpret_cast<const short8*>(brow + k + 64 * 8));
+    bf16x8 bv = *reinterpret_cast<const bf16x8*>(&cur_);
+    float bfv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bfv[j] = bf2f(bv.v[j]);
+#pragma unroll
+    for (int m = 0; m < MM; ++m) {
+      bf16x8 av = *reinterpret_cast<const bf16x8*>(A + (long long)m * K + k);
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += bf2f(av.v[j]) * bfv[j];
+      acc[m] += s;
+    }
+    cur_ = nxt_;
+  }
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    float v = wave_reduce_sum(acc[m]);
+    if (lane == 0 && m < M) C[(long long)m * N + n] = f2bf(v);
+  }
+}
+
 // concrete instantiations with C linkage for the bindings TU
 #define GEMV2_INST(MM)                                                        \
   extern "C" __global__ void __launch_bounds__(256)                           \
   gemv_bt_bf16_v2_m##MM(const ushort* A, const ushort* B, ushort* C, int M,   \
                         int N, int K) {                                       \
-    const int wid = threadIdx.x >> 6;                                         \
-    const int lane = threadIdx.x & 63;                                        \
-    const int n = blockIdx.x * 4 + wid;                                       \
-    if (n >= N) return;                                                       \
-    const ushort* brow = B + (long long)n * K;                                \
-    float acc[MM];                                                            \
-    _Pragma("unroll") for (int m = 0; m < MM; ++m) acc[m] = 0.f;              \
-    /* 2-deep software pipeline: the runtime-K loop otherwise keeps ONE     \
-       weight load in flight per lane (latency-bound on the small rows) */   \
-    short8 cur_ = __builtin_nontemporal_load(                                 \
-        reinterpret_cast<const short8*>(brow + lane * 8));                    \
-    for (int k = lane * 8; k < K; k += 64 * 8) {                              \
-      short8 nxt_;                                                            \
-      if (k + 64 * 8 < K)                                                     \
-        nxt_ = __builtin_nontemporal_load(                                    \
-            reinterpret_cast<const short8*>(brow + k + 64 * 8));              \
-      bf16x8 bv = *reinterpret_cast<const bf16x8*>(&cur_);                    \
-      float bfv[8];                                                           \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) bfv[j] = bf2f(bv.v[j]);   \
-      _Pragma("unroll") for (int m = 0; m < MM; ++m) {                        \
-        bf16x8 av = *reinterpret_cast<const bf16x8*>(A + (long long)m * K + k); \
-        float s = 0.f;                                                        \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j)                         \
-            s += bf2f(av.v[j]) * bfv[j];                                      \
-        acc[m] += s;                                                          \
-      }                                                                       \
-      cur_ = nxt_;                                                            \
-    }                                                                         \
-    _Pragma("unroll") for (int m = 0; m < MM; ++m) {                          \
-      float v = wave_reduce_sum(acc[m]);                                      \
-      if (lane == 0 && m < M) C[(long long)m * N + n] = f2bf(v);              \
-    }                                                                         \
+    gemv2_body<MM>(A, B, C, M, N, K);                                         \
   }
 
 // ---------------------------------------------------------------------------
@@ -322,8 +129,8 @@ gemm_bt_bf16_256_kernel(const ushort* __restrict__ A, const ushort* __restrict__
 // per row per slot), x is staged to LDS once up front; counted
 // s_waitcnt vmcnt(8*slots in flight) before each barrier (wait-then-barrier).
 //
-// gemv3_body (one slot per barrier, ring of RD) is the first form and is no
-// longer launched; it needs M == 1, K % 512 == 0, N % 8 == 0.
+// The first form, gemv3_body (one slot per barrier, never launched since), is
+// in this file at commit 6c7e738.
 // gemv3_body2 (two slots per barrier, ring of 6) serves every launched
 // kernel — gemv_bt_bf16_v3_m1 (K <= 4096), gemv_bt_bf16_v3w_m1 and
 // swiglu_gemv_bt_bf16_m1 (K <= 14336).  Constraints: M == 1,
@@ -332,114 +139,6 @@ gemm_bt_bf16_256_kernel(const ushort* __restrict__ A, const ushort* __restrict__
 // K <= XCAP, N % 8 == 0 (grid N/8, every block reads 8 full rows).
 // ---------------------------------------------------------------------------
 #define GV3_KW 512         /* chunk elems per row per slot */
-
-template <int XCAP, int RD>
-static __device__ __forceinline__ void gemv3_body(
-    const ushort* __restrict__ A, const ushort* __restrict__ B,
-    ushort* __restrict__ C, int N, int K) {
-  // 8 rows per block, slot = 8 rows x 1 KiB = 8 KiB, ring of RD slots.
-  // K <= 4096: ring 7*8 + x 8 = 64 KiB -> TWO blocks/CU (one block's
-  // barrier/latency stalls hide under the other's stream).  K <= 14336
-  // (down-proj): x is 28 KiB -> one block/CU.
-  const int n0 = blockIdx.x * 8;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-
-  __shared__ __attribute__((aligned(16))) ushort gv3_smem[RD * 8 * GV3_KW + XCAP];
-  ushort* slots = gv3_smem;
-  ushort* x_lds = gv3_smem + RD * 8 * GV3_KW;
-
-  const int nslots = K / GV3_KW;
-
-  if (wid < 3) {
-    // stage x (1 KiB chunks, lane-linear)
-    for (int c = wid; c < nslots; c += 3)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)
-              (A + (long long)c * GV3_KW + lane * 8),
-          (__attribute__((address_space(3))) unsigned int*)
-              (x_lds + (long long)c * GV3_KW + lane * 8),
-          16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    // loader prologue: slots 0..RD-2 (8 nt glds each), then slot 0 landed
-    for (int t = 0; t < RD - 1 && t < nslots; ++t) {
-      const ushort* src0 = B + (long long)n0 * K + (long long)t * GV3_KW;
-      ushort* dst0 = slots + (t % RD) * 8 * GV3_KW;
-#pragma unroll
-      for (int r = 0; r < 8; ++r)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)
-                (src0 + (long long)r * K + lane * 8),
-            (__attribute__((address_space(3))) unsigned int*)
-                (dst0 + r * GV3_KW + lane * 8),
-            16, 0, 2 /* nt */);
-    }
-    const int inflight0 = ((RD - 2) < (nslots - 1) ? (RD - 2) : (nslots - 1));
-    switch (inflight0 < 0 ? 0 : inflight0) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-    }
-  }
-  __builtin_amdgcn_s_barrier();
-
-  // consumer: wave w owns rows 2w, 2w+1; reads are lane-linear b128
-  // (conflict-free — the j*32 strided form measured a 16-way bank storm)
-  float acc0 = 0.f, acc1 = 0.f;
-  const int r0 = wid * 2;
-  for (int t = 0; t < nslots; ++t) {
-    const ushort* slot = slots + (t % RD) * 8 * GV3_KW;
-    bf16x8 xv = *reinterpret_cast<const bf16x8*>(
-        x_lds + (long long)t * GV3_KW + lane * 8);
-    bf16x8 w0 = *reinterpret_cast<const bf16x8*>(slot + r0 * GV3_KW + lane * 8);
-    bf16x8 w1 = *reinterpret_cast<const bf16x8*>(slot + (r0 + 1) * GV3_KW + lane * 8);
-    float xf[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) xf[e] = bf2f(xv.v[e]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc0 += bf2f(w0.v[e]) * xf[e];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc1 += bf2f(w1.v[e]) * xf[e];
-    if (wid == 3) {
-      const int nxt = t + RD - 1;
-      if (nxt < nslots) {
-        const ushort* src0 = B + (long long)n0 * K + (long long)nxt * GV3_KW;
-        ushort* dst0 = slots + (nxt % RD) * 8 * GV3_KW;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          __builtin_amdgcn_global_load_lds(
-              (const __attribute__((address_space(1))) unsigned int*)
-                  (src0 + (long long)r * K + lane * 8),
-              (__attribute__((address_space(3))) unsigned int*)
-                  (dst0 + r * GV3_KW + lane * 8),
-              16, 0, 2);
-      }
-      const int last = (nxt < nslots ? nxt : nslots - 1);
-      const int inflight = last - (t + 1);
-      switch (inflight < 0 ? 0 : inflight) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-      }
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
-
-  acc0 = wave_reduce_sum(acc0);
-  acc1 = wave_reduce_sum(acc1);
-  if (lane == 0 && n0 + r0 < N) C[n0 + r0] = f2bf(acc0);
-  if (lane == 0 && n0 + r0 + 1 < N) C[n0 + r0 + 1] = f2bf(acc1);
-}
 
 // two slots per barrier round: the 1-slot cadence measured ~0.7 us/slot
 // against a 0.32 us fill (barrier+loader-wait dominated); pairing slots
@@ -773,8 +472,14 @@ GEMV2_INST(16)
 // reduction — one kernel replaces (fused_add_rmsnorm + gemv), two of the
 // ~5 us launches per decode layer.  Block 0 additionally writes
 // res_out[m] = t[m] (a separate buffer: no cross-block write/read race).
+//
+// Still a macro, unlike the other GEMVs: as a template body the m16 instance
+// rounds differently.  A device function is optimised before it is inlined,
+// without the kernel's __launch_bounds__, so only one of dot[16] / ss[16] is
+// promoted to a vector there; the loop then vectorises differently and the
+// backend fuses 105 of its mul+add pairs into fma that are separate here.
 // ---------------------------------------------------------------------------
-#define GEMV_NORM_INST(MM)                                                    \
+#define GEMV_NORM_INST(MM)                                                   \
   extern "C" __global__ void __launch_bounds__(256)                           \
   gemv_norm_bt_bf16_m##MM(const ushort* x, const ushort* res_in,              \
                           const ushort* normw, const ushort* B, ushort* C,    \

@@ -142,6 +142,20 @@ def test_grouped_gemm_kernel(dev, gen, hip_impl, sizes, N, K, offsets):
     ko.check_grouped_gemm(ops.grouped_gemm_bt, sizes, N, K, dev, gen, offsets=offsets)
 
 
+def test_grouped_gemm_one_expert_equals_dense(dev, gen, hip_impl):
+    """One expert whose segment covers every row is the dense GEMM: the
+    grouped kernel and gemm_bt_bf16_kernel (256 x 256 is 2 x 2 tiles of 128)
+    run one pipeline body, the same operations in the same order, so the
+    outputs are equal bit for bit.  K = 192: three K-tiles."""
+    M, N, K = 256, 256, 192
+    a = ko.rand_bf16(gen, M, K).to(dev)
+    w = ko.rand_bf16(gen, 1, N, K).to(dev)
+    got = ops.grouped_gemm_bt(a, w, [0, M])
+    exp = ops.hip_ext().gemm_bt(a, w[0])
+    assert tuple(got.shape) == (M, N)
+    assert torch.equal(got, exp)
+
+
 # ---------------- quantizers ----------------
 @pytest.mark.parametrize("K", [8, 64, 2048, 2056, 4096])
 @pytest.mark.parametrize("rows", [1, 3, 64])
