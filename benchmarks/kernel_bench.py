@@ -239,6 +239,39 @@ def bench_attn():
         print(f"  torch sdpa:        {flops / tsdpa / 1e12:7.1f} TF/s")
 
 
+def bench_attn_packed(rounds=5):
+    """The packed prefill attention of the headline shape (B4 H32 Hk8 S2048,
+    skips 0/448/448/448), V^T route against V-rows route, alternating in one
+    session: attn_fwd_v5_packed_rm on a ready V^T, vt_from_qkv_packed (the
+    pass the new kernel makes unnecessary), and attn_fwd_v5_packed_rm_qkv.
+    Device time per call in us, three rotating input sets."""
+    from senweaver_amd.engine.prefix_plan import plan_from_skips
+    dev = torch.device("cuda:0")
+    ext = ops.hip_ext()
+    B, H, Hk, S, D = 4, 32, 8, 2048, 128
+    plan = plan_from_skips((0,) * B, (0, 448, 448, 448), S)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    skip, base, owner = i32(plan.skip), i32(plan.base), i32(plan.owner)
+    scale = 1.0 / math.sqrt(D)
+    sets = []
+    for _ in range(3):
+        q = torch.randn(B, H, S, D, dtype=torch.bfloat16, device=dev)
+        k = torch.randn(B, Hk, S, D, dtype=torch.bfloat16, device=dev)
+        qkv = torch.randn(plan.Tp, (H + 2 * Hk) * D, dtype=torch.bfloat16, device=dev)
+        vt = ext.vt_from_qkv_packed(qkv, H, Hk, D, B, S, skip, base, owner)
+        sets.append((q, k, qkv, vt, torch.empty(plan.Tp, H * D, dtype=torch.bfloat16, device=dev)))
+    old = lambda i: ext.attn_fwd_v5_packed_rm(sets[i][0], sets[i][1], sets[i][3], scale,
+                                              skip, base, plan.Tp, sets[i][4])
+    tr = lambda i: ext.vt_from_qkv_packed(sets[i][2], H, Hk, D, B, S, skip, base, owner)
+    new = lambda i: ext.attn_fwd_v5_packed_rm_qkv(sets[i][0], sets[i][1], sets[i][2], H, Hk,
+                                                  scale, skip, base, owner, plan.Tp, sets[i][4])
+    print(f"ATTN packed B{B} H{H} Hk{Hk} S{S} skips {plan.skip} Tp {plan.Tp}: us per call")
+    print("  round   V^T attn   V^T pass   sum     V-rows attn")
+    for r in range(rounds):
+        t_old, t_tr, t_new = (event_us(f, 3, warmup=3, iters=30) for f in (old, tr, new))
+        print(f"  {r:5d}   {t_old:8.1f}   {t_tr:8.1f}   {t_old + t_tr:6.1f}   {t_new:8.1f}")
+
+
 def bench_gemv():
     """Decode GEMV family: bf16 v2/v3(engine) and fp8/mxfp8-weight forms."""
     dev = torch.device("cuda:0")
@@ -295,6 +328,8 @@ if __name__ == "__main__":
         bench_tile()
     if which in ("all", "attn"):
         bench_attn()
+    if which == "attn_packed":
+        bench_attn_packed()
     if which in ("all", "gemv"):
         bench_gemv()
     if which in ("all", "mem"):

@@ -17,9 +17,10 @@ the whole candidate prompt.  A plan stores such a prefix once:
       s <  skip[b]:  base[owner[b]] + s
 
 ``Tp = sum(S - skip[b])`` rows go through every row-wise op (GEMMs, norms,
-SwiGLU) instead of ``B * S``; only rope_scatter, the V^T transpose and the
-attention epilogue translate between packed rows and the [B, H, S, D]
-attention layouts (ops/csrc/README.md).  Pure Python: no torch import, the
+SwiGLU) instead of ``B * S``; only rope_scatter, the attention kernel's V
+staging (the V^T transpose where the v5 kernel does not run) and its epilogue
+translate between packed rows and the [B, H, S, D] attention layouts
+(ops/csrc/README.md).  Pure Python: no torch import, the
 plan is a handful of ints per row.
 """
 

@@ -299,14 +299,14 @@ class LlamaModel:
             qb, kb = ops.rope_scatter_qkv_packed(
                 qkv, self.cos_sin, positions, self.local_heads,
                 self.local_kv_heads, c.head_dim, B, S, skip, base, owner)
-            vt = ops.vt_from_qkv_packed(qkv, self.local_heads,
-                                        self.local_kv_heads, c.head_dim, B, S,
-                                        skip, base, owner)
-            # packed attention writes O row-major [Tp, Hq*D]: o_proj is a
-            # plain projection (reading A as a transposed view of O^T cost
-            # the GEMM 16%, profiles/gemm_lt_tuning.txt)
-            attn = ops.attn_fwd_packed(qb, kb, vt, self.scale, skip, base, Tp,
-                                       flat_idx)
+            # V stays where the qkv GEMM wrote it: the attention kernel reads
+            # its rows from there (profiles/attn_v_rows.txt).  Packed
+            # attention writes O row-major [Tp, Hq*D]: o_proj is a plain
+            # projection (reading A as a transposed view of O^T cost the
+            # GEMM 16%, profiles/gemm_lt_tuning.txt)
+            attn = ops.attn_fwd_packed_qkv(
+                qb, kb, qkv, self.local_heads, self.local_kv_heads,
+                c.head_dim, self.scale, skip, base, owner, Tp, flat_idx)
             if self.quant == "bf16" and not attn.is_cuda:
                 # CPU: the bf16 matmul the unpacked path's o_proj uses, so
                 # packed and unpacked stay bit-equal there

@@ -226,6 +226,26 @@ def attn_fwd_packed(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
     return ot.permute(0, 3, 1, 2).reshape(B * S, H * D).index_select(0, flat_idx)
 
 
+def attn_fwd_packed_qkv(qb: torch.Tensor, kb: torch.Tensor, qkv: torch.Tensor,
+                        Hq: int, Hk: int, D: int, scale: float, skip, base,
+                        owner, Tp: int, flat_idx) -> torch.Tensor:
+    """attn_fwd_packed with V taken from the packed ``qkv`` rows themselves.
+
+    Where attn_fwd_packed runs the v5 kernel, the same kernel body reads each
+    key's V row straight out of ``qkv`` (a transposing LDS read gives the MFMA
+    its operand): no V^T tensor and no transpose pass, and bit for bit
+    attn_fwd_packed's O.  Everywhere else (CPU, tiny grids, SENWEAVER_ATTN=v2)
+    it is vt_from_qkv_packed + attn_fwd_packed, so packing never changes which
+    numerics a shape gets."""
+    B, H, S, _ = qb.shape
+    if _on_gpu(qb) and _ATTN_IMPL != "v2" and ((S + 255) // 256) * B * H >= 512:
+        return hip_ext().attn_fwd_v5_packed_rm_qkv(
+            qb.contiguous(), kb.contiguous(), qkv.contiguous(), Hq, Hk, scale,
+            skip, base, owner, Tp)
+    vt = vt_from_qkv_packed(qkv, Hq, Hk, D, B, S, skip, base, owner)
+    return attn_fwd_packed(qb, kb, vt, scale, skip, base, Tp, flat_idx)
+
+
 def swiglu(gateup: torch.Tensor, out_rows: Optional[int] = None) -> torch.Tensor:
     """silu(gate) * up.  With ``out_rows`` > rows (2-D input) the result has
     out_rows rows, zero past the input's: the next GEMM can run at a row

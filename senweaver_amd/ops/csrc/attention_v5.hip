@@ -32,6 +32,7 @@
 #include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
+typedef __attribute__((ext_vector_type(4))) short short4v;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define V5_KVBLK 64
@@ -76,6 +77,37 @@ static __device__ __forceinline__ short8 v5_read(const ushort* lds_tile,
   return *reinterpret_cast<const short8*>(lds_tile + (row * chunks_per_row + phys) * 8);
 }
 
+// Row-major V tile (VROWS): 64 keys x 128 d, plain 256-byte rows.  The
+// 16-byte chunk ch of key row r sits at physical chunk ch ^ v5_vx(r): with
+// that XOR the transposed 32x32x16 operand read below touches every bank of a
+// 32-lane half exactly once.
+static __device__ __forceinline__ int v5_vx(int r) {
+  return ((r & 3) << 2) | ((r >> 2) & 3);
+}
+
+// PV operand from the row-major tile: lane (l31, lhi) gets
+// V[kvg + 8*lhi + 0..7][db*32 + l31], what v5_read hands it from a V^T tile.
+// ds_read_b64_tr_b16 gathers, per 16 lanes, a block of 4 keys x 16 d and
+// gives lane i the 4 keys of column i; lane 4q+p supplies the address of key
+// row q, columns 4p .. 4p+3.  Two reads (keys +0..3 and +4..7) make the
+// operand.  Every lane of the wave must be active, and every address is a
+// multiple of 8 bytes.
+static __device__ __forceinline__ short8 v5_read_tr(const ushort* v_lds,
+                                                    int lane, int kvg, int db) {
+  const int p = lane & 3, q = (lane >> 2) & 3, hh = (lane >> 4) & 1;
+  const int lhi = lane >> 5;
+  short4v part[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = kvg + 8 * lhi + 4 * j + q;
+    const int ch = db * 4 + 2 * hh + (p >> 1);
+    const int off = row * 128 + (ch ^ v5_vx(row)) * 8 + 4 * (p & 1);
+    part[j] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (__attribute__((address_space(3))) short4v*)(v_lds + off));
+  }
+  return __builtin_shufflevector(part[0], part[1], 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 static __device__ __forceinline__ unsigned v5_cvt_pk_bf16(float lo, float hi) {
   unsigned r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
@@ -96,6 +128,34 @@ static __device__ __forceinline__ float v5_exp2(float x) {
   return r;
 }
 
+// Block order for a 1-D grid of nqb * H * B blocks.  The hardware deals
+// consecutive workgroups round-robin over the 8 XCDs, each with an L2 of its
+// own.  The nqb * (H / Hk) blocks of one (batch, kv head) read the same K and
+// V, so they all go to one XCD: group g runs on XCD g % 8, and inside an XCD
+// the blocks run heaviest first (q block slowest, descending), the heads of a
+// group next to each other.  A bijection whenever B * Hk is a multiple of 8;
+// otherwise the order of the 3-D grid (q block fastest, descending) is kept.
+static __device__ __forceinline__ void attn5_xcd_block(int B, int H, int Hk,
+                                                       int nqb, int& qb,
+                                                       int& h, int& b) {
+  const int i = blockIdx.x;
+  const int groups = B * Hk;
+  if (groups % 8 == 0) {
+    const int rep = H / Hk;
+    const int per_rank = (groups / 8) * rep;  // blocks per XCD and q block
+    const int j = i / 8;
+    const int r = j % per_rank;
+    const int g = i % 8 + 8 * (r / rep);
+    qb = nqb - 1 - j / per_rank;
+    h = (g % Hk) * rep + r % rep;
+    b = g / Hk;
+  } else {
+    qb = nqb - 1 - i % nqb;
+    h = (i / nqb) % H;
+    b = i / (nqb * H);
+  }
+}
+
 // PACK (prefix-packed prefill): Q/K/V^T are indexed as usual, but query rows
 // below skip[b] belong to the group leader and are not recomputed — a block
 // entirely below skip[b] exits before any LDS traffic or barrier, and the
@@ -106,15 +166,39 @@ static __device__ __forceinline__ float v5_exp2(float x) {
 // A.  (Staging the rows through LDS for fully coalesced 16-byte stores was
 // tried and timed the same, 322.8 against 321.6 us in situ; isolated, both
 // layouts run within 1 us of each other.  The plain stores stay.)
-template <int PACK>
+//
+// VROWS (with PACK): there is no V^T.  VT is the packed qkv GEMM output
+// [Tq, ld] itself, and key s of batch row b is the 256 contiguous bytes at
+// row packed_src_row(b, s), column v_off + kvh*128.  The tile is staged
+// row-major (v5_vx) and the PV operand comes out of ds_read_b64_tr_b16
+// (v5_read_tr): the same operands in the same MFMA order, so the same bits.
+// A row that a bad plan sends outside [0, Tq) reads row 0 instead.
+//
+// The VROWS kernel is also the one that got the two scheduling changes below
+// (measured with it, profiles/attn_v_rows.txt); the V^T instances keep their
+// code as it was.
+//
+// WSKIP: a wave does no QK^T, softmax or PV for a tile that lies wholly above
+// its own 32 query rows (the last three tiles of a block's diagonal, for 2, 4
+// and 6 of the 8 waves).  Such a tile has p = 0 everywhere and defer-max
+// holds, so it adds +-0 to O and 0 to the row sum: skipping it is exact.  The
+// wave still stages its share of the next tile and meets the barrier.
+//
+// XCD: a 1-D grid, mapped by attn5_xcd_block.
+template <int PACK, bool VROWS = false>
 static __device__ __forceinline__ void attn5_body(
     const ushort* __restrict__ Q, const ushort* __restrict__ K,
     const ushort* __restrict__ VT, ushort* __restrict__ OT, int B, int H,
     int Hk, int S, float scale, const int* __restrict__ pk_skip = nullptr,
-    const int* __restrict__ pk_base = nullptr, int Tp = 0) {
-  const int qb = gridDim.x - 1 - blockIdx.x;  // heaviest-first
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
+    const int* __restrict__ pk_base = nullptr, int Tp = 0,
+    const int* __restrict__ pk_owner = nullptr, long long ld = 0,
+    long long v_off = 0, long long Tq = 0) {
+  static_assert(!VROWS || PACK == 2, "VROWS reads packed qkv rows");
+  constexpr bool WSKIP = VROWS, XCD = VROWS;
+  int qb = gridDim.x - 1 - blockIdx.x;  // heaviest-first
+  int h = blockIdx.y;
+  int b = blockIdx.z;
+  if (XCD) attn5_xcd_block(B, H, Hk, (S + V5_QBLK - 1) / V5_QBLK, qb, h, b);
   int skip = 0;
   if (PACK) {
     // block-uniform early-out: every query row of this block is a prefix
@@ -127,7 +211,24 @@ static __device__ __forceinline__ void attn5_body(
 
   const ushort* Qh = Q + (((long long)b * H + h) * S) * D;
   const ushort* Kh = K + (((long long)b * Hk + kvh) * S) * D;
-  const ushort* VTh = VT + (((long long)b * Hk + kvh) * D) * S;
+  const ushort* VTh = VROWS ? VT + v_off + (long long)kvh * D
+                             : VT + (((long long)b * Hk + kvh) * D) * S;
+  // VROWS: packed_src_row(b, s) is pre0 + s below skip and own0 + s from it
+  // on; the block-uniform parts are fetched once
+  long long pre0 = 0, own0 = 0;
+  if (VROWS) {
+    pre0 = packed_src_row(b, 0, B, pk_skip, pk_base, pk_owner);
+    own0 = pk_base[b];
+  }
+  // source of the chunk that belongs in slot s (key row s / 16, physical
+  // chunk s % 16) of the V tile that starts at key kv0
+  auto v_rows_src = [&](int kv0, int s) -> const ushort* {
+    const int r = s >> 4;
+    const int key = kv0 + r;
+    long long tr = (key < skip ? pre0 : own0) + key;
+    if ((key < skip && pre0 < 0) || tr < 0 || tr >= Tq) tr = 0;
+    return VTh + tr * ld + ((s & 15) ^ v5_vx(r)) * 8;
+  };
   ushort* OTh = OT + (((long long)b * H + h) * D) * S;
 
   const int tid = threadIdx.x;
@@ -137,6 +238,7 @@ static __device__ __forceinline__ void attn5_body(
   const int lhi = lane >> 5;
   const int q0 = qb * V5_QBLK + wid * 32;  // 32 q rows per wave
   const int q_lane = q0 + l31;
+  const int q0_wave = qb * V5_QBLK + __builtin_amdgcn_readfirstlane(wid) * 32;
   const bool live = q_lane < S;
 
   __shared__ __attribute__((aligned(16))) ushort smem[2][V5_KVBLK * 128 + 128 * V5_KVBLK];
@@ -169,7 +271,7 @@ static __device__ __forceinline__ void attn5_body(
   for (int s0 = 0; s0 < V5_CHUNKS; s0 += V5_NT) {
     const int s = s0 + tid;
     if (s >= V5_CHUNKS) break;
-    v5_glds(v5_src(VTh, S, 8, s / 8, s % 8),
+    v5_glds(VROWS ? v_rows_src(0, s) : v5_src(VTh, S, 8, s / 8, s % 8),
             smem[0] + V5_KVBLK * 128 + (long long)(s0 + (tid & ~63)) * 8);
   }
   __syncthreads();
@@ -178,22 +280,27 @@ static __device__ __forceinline__ void attn5_body(
     const bool more = kv0 + V5_KVBLK < kv_end;
     const ushort* k_lds = smem[buf];
     const ushort* vt_lds = smem[buf] + V5_KVBLK * 128;
+    // wave-uniform, and known to the compiler as such: the transposed reads
+    // of the waves that do work need all their lanes
+    const bool work = !WSKIP || kv0 <= q0_wave + 31;
 
-    __builtin_amdgcn_s_setprio(1);
     f32x16 st[2];
+    if (work) {
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      f32x16 acc;
+      for (int sub = 0; sub < 2; ++sub) {
+        f32x16 acc;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-      for (int stp = 0; stp < 8; ++stp) {
-        short8 kf = v5_read(k_lds, sub * 32 + l31, stp * 2 + lhi, 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[stp], acc, 0, 0, 0);
+        for (int stp = 0; stp < 8; ++stp) {
+          short8 kf = v5_read(k_lds, sub * 32 + l31, stp * 2 + lhi, 16);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[stp], acc, 0, 0, 0);
+        }
+        st[sub] = acc;
       }
-      st[sub] = acc;
+      __builtin_amdgcn_s_setprio(0);
     }
-    __builtin_amdgcn_s_setprio(0);
 
     // issue the next tile's loads to registers: the K rows of this tile are
     // consumed, and its V^T stays live in LDS until PV
@@ -205,54 +312,53 @@ static __device__ __forceinline__ void attn5_body(
       for (int c = 0; c < V5_KC; ++c) {
         const int s = tid + c * V5_NT;
         stg[c] = *reinterpret_cast<const short8*>(v5_src(Kn, D, 16, s / 16, s % 16));
-        stg[V5_KC + c] = *reinterpret_cast<const short8*>(v5_src(VTn, S, 8, s / 8, s % 8));
+        stg[V5_KC + c] = *reinterpret_cast<const short8*>(
+            VROWS ? v_rows_src(kv0 + V5_KVBLK, s) : v5_src(VTn, S, 8, s / 8, s % 8));
       }
     }
 
     float vals[32];
-    float tile_max = -INFINITY;
-    const float scl = scale * 1.44269504f;  // exp2 domain
-    const bool interior = kv0 + V5_KVBLK - 1 <= q0;
-    if (interior) {
+    float m_new = m_run, alpha = 1.f;
+    if (work) {
+      float tile_max = -INFINITY;
+      const float scl = scale * 1.44269504f;  // exp2 domain
+      const bool interior = kv0 + V5_KVBLK - 1 <= q0;
+      if (interior) {
 #pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
+        for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float v = st[sub][r] * scl;
-          vals[sub * 16 + r] = v;
-          tile_max = v5_max(tile_max, v);
-        }
-    } else {
+          for (int r = 0; r < 16; ++r) {
+            const float v = st[sub][r] * scl;
+            vals[sub * 16 + r] = v;
+            tile_max = v5_max(tile_max, v);
+          }
+      } else {
 #pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
+        for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kv = kv0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-          float v = st[sub][r] * scl;
-          if (kv > q_lane) v = -INFINITY;
-          vals[sub * 16 + r] = v;
-          tile_max = v5_max(tile_max, v);
-        }
-    }
-    tile_max = v5_max(tile_max, __shfl_xor(tile_max, 32, 64));
-    // wave-uniform: every lane's tile max within the threshold of its running
-    // max (first tile: m_run = -inf makes the difference +inf -> no defer)
-    const bool defer = __all((int)(tile_max - m_run <= 11.54f));
-    float m_new, alpha;
-    if (defer) {
-      m_new = m_run;
-      alpha = 1.f;
-    } else {
-      m_new = fmaxf(m_run, tile_max);
-      alpha = (m_run == -INFINITY) ? 0.f : v5_exp2(m_run - m_new);
-    }
-    float rsum = 0.f;
-    m_run = m_new;
-    if (!defer) {
+          for (int r = 0; r < 16; ++r) {
+            const int kv = kv0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            float v = st[sub][r] * scl;
+            if (kv > q_lane) v = -INFINITY;
+            vals[sub * 16 + r] = v;
+            tile_max = v5_max(tile_max, v);
+          }
+      }
+      tile_max = v5_max(tile_max, __shfl_xor(tile_max, 32, 64));
+      // wave-uniform: every lane's tile max within the threshold of its running
+      // max (first tile: m_run = -inf makes the difference +inf -> no defer)
+      const bool defer = __all((int)(tile_max - m_run <= 11.54f));
+      if (!defer) {
+        m_new = fmaxf(m_run, tile_max);
+        alpha = (m_run == -INFINITY) ? 0.f : v5_exp2(m_run - m_new);
+      }
+      m_run = m_new;
+      if (!defer) {
 #pragma unroll
-      for (int db = 0; db < 4; ++db)
+        for (int db = 0; db < 4; ++db)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
+          for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
+      }
     }
 
     // park the fetched tile in the idle buffer before PV (waits the loads
@@ -267,41 +373,45 @@ static __device__ __forceinline__ void attn5_body(
       }
     }
 
+    if (work) {
+      float rsum = 0.f;
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
+      for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const int base = sub * 16 + g * 8;
-        float p[8];
+        for (int g = 0; g < 2; ++g) {
+          const int base = sub * 16 + g * 8;
+          float p[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          p[i] = v5_exp2(vals[base + i] - m_new);
-          rsum += p[i];
+          for (int i = 0; i < 8; ++i) {
+            p[i] = v5_exp2(vals[base + i] - m_new);
+            rsum += p[i];
+          }
+          unsigned x0 = v5_cvt_pk_bf16(p[0], p[1]);
+          unsigned y0 = v5_cvt_pk_bf16(p[4], p[5]);
+          unsigned x1 = v5_cvt_pk_bf16(p[2], p[3]);
+          unsigned y1 = v5_cvt_pk_bf16(p[6], p[7]);
+          auto r0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
+          auto r1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
+          short8 pfrag;
+          unsigned* pw = reinterpret_cast<unsigned*>(&pfrag);
+          pw[0] = (unsigned)r0[0];
+          pw[1] = (unsigned)r1[0];
+          pw[2] = (unsigned)r0[1];
+          pw[3] = (unsigned)r1[1];
+          const int kvg = sub * 32 + g * 16;
+          __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+          for (int db = 0; db < 4; ++db) {
+            short8 vf = VROWS ? v5_read_tr(vt_lds, lane, kvg, db)
+                              : v5_read(vt_lds, db * 32 + l31, (kvg >> 3) + lhi, 8);
+            o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pfrag, o_acc[db], 0, 0, 0);
+          }
+          __builtin_amdgcn_s_setprio(0);
         }
-        unsigned x0 = v5_cvt_pk_bf16(p[0], p[1]);
-        unsigned y0 = v5_cvt_pk_bf16(p[4], p[5]);
-        unsigned x1 = v5_cvt_pk_bf16(p[2], p[3]);
-        unsigned y1 = v5_cvt_pk_bf16(p[6], p[7]);
-        auto r0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto r1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        short8 pfrag;
-        unsigned* pw = reinterpret_cast<unsigned*>(&pfrag);
-        pw[0] = (unsigned)r0[0];
-        pw[1] = (unsigned)r1[0];
-        pw[2] = (unsigned)r0[1];
-        pw[3] = (unsigned)r1[1];
-        const int kvg = sub * 32 + g * 16;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          short8 vf = v5_read(vt_lds, db * 32 + l31, (kvg >> 3) + lhi, 8);
-          o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pfrag, o_acc[db], 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
       }
+      rsum += __shfl_xor(rsum, 32, 64);
+      l_run = l_run * alpha + rsum;
     }
-    rsum += __shfl_xor(rsum, 32, 64);
-    l_run = l_run * alpha + rsum;
 
     __syncthreads();
     buf ^= 1;
@@ -380,4 +490,21 @@ attn_fwd_v5_packed_rm_kernel(const ushort* __restrict__ Q,
                              int S, float scale, const int* __restrict__ skip,
                              const int* __restrict__ base, int Tp) {
   attn5_body<2>(Q, K, VT, O, B, H, Hk, S, scale, skip, base, Tp);
+}
+
+// The row-major packed kernel reading V straight from the packed qkv rows
+// (attn5_body's VROWS): no V^T tensor and no transpose pass before it.
+// Launched on a 1-D grid of ceil(S / 256) * H * B blocks.
+extern "C" __global__ void __launch_bounds__(512)
+attn_fwd_v5_packed_rm_qkv_kernel(const ushort* __restrict__ Q,
+                                 const ushort* __restrict__ K,
+                                 const ushort* __restrict__ qkv, long long ld,
+                                 long long v_off, long long Tq,
+                                 ushort* __restrict__ O, int B, int H, int Hk,
+                                 int S, float scale,
+                                 const int* __restrict__ skip,
+                                 const int* __restrict__ base,
+                                 const int* __restrict__ owner, int Tp) {
+  attn5_body<2, true>(Q, K, qkv, O, B, H, Hk, S, scale, skip, base, Tp, owner,
+                      ld, v_off, Tq);
 }

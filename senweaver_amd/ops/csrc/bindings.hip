@@ -708,6 +708,56 @@ torch::Tensor attn_fwd_v5_packed_rm(torch::Tensor q, torch::Tensor k,
   return attn_packed_launch(q, k, vt, scale, skip, base, Tp, true, out);
 }
 
+// attn_fwd_v5_packed_rm with V read from the packed qkv rows [Tq, ld] (the
+// fused qkv GEMM's output) in place of a V^T made by vt_from_qkv_packed: the
+// same O [Tp, Hq*D], bit for bit, without the transpose pass.
+torch::Tensor attn_fwd_v5_packed_rm_qkv(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor qkv, int64_t Hq,
+                                        int64_t Hk, double scale,
+                                        torch::Tensor skip, torch::Tensor base,
+                                        torch::Tensor owner, int64_t Tp,
+                                        c10::optional<torch::Tensor> out) {
+  check_bf16(q, "q");
+  check_bf16(k, "k");
+  check_bf16(qkv, "qkv");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && qkv.dim() == 2,
+              "attn_fwd_v5_packed_rm_qkv: q [B,H,S,D], k [B,Hk,S,D], qkv [Tq,ld]");
+  const int64_t B = q.size(0), S = q.size(2), D = q.size(3);
+  TORCH_CHECK(q.size(1) == Hq && Hk > 0 && Hq % Hk == 0 && D == 128 && S % 128 == 0,
+              "attn_fwd_v5_packed_rm_qkv: needs D == 128, S % 128 == 0, Hq % Hk == 0");
+  TORCH_CHECK(k.size(0) == B && k.size(1) == Hk && k.size(2) == S && k.size(3) == D,
+              "attn_fwd_v5_packed_rm_qkv: k must be [B,Hk,S,D]");
+  const long long Tq = qkv.size(0);
+  const long long ld = qkv.size(1);
+  TORCH_CHECK(Tq > 0 && Tq <= B * S && ld % 8 == 0 && ld >= (Hq + 2 * Hk) * D,
+              "attn_fwd_v5_packed_rm_qkv: qkv must hold (0, B*S] rows of at least "
+              "(Hq+2Hk)*D columns, row length a multiple of 8");
+  TORCH_CHECK(Tp > 0 && Tp <= B * S && B * S < (1LL << 31),
+              "attn_fwd_v5_packed_rm_qkv: Tp must be in (0, B*S]");
+  check_plan(skip, B, "skip");
+  check_plan(base, B, "base");
+  check_plan(owner, B, "owner");
+  const std::vector<int64_t> shape{Tp, Hq * D};
+  torch::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    check_bf16(o, "out");
+    TORCH_CHECK(o.sizes().vec() == shape, "attn_fwd_v5_packed_rm_qkv: out has the wrong shape");
+    TORCH_CHECK((uintptr_t)o.data_ptr() % 16 == 0, "attn_fwd_v5_packed_rm_qkv: out must be 16-byte aligned");
+  } else {
+    o = torch::empty(shape, q.options());
+  }
+  const long long v_off = (Hq + Hk) * D;
+  const int nqb = (int)((S + 255) / 256);
+  // 1-D grid: the kernel orders its blocks over the XCDs itself
+  attn_fwd_v5_packed_rm_qkv_kernel<<<dim3((unsigned)(nqb * Hq * B)), dim3(512), 0, cur_stream()>>>(
+      bf16_ptr(q), bf16_ptr(k), bf16_ptr(qkv), ld, v_off, Tq, bf16_mut(o),
+      (int)B, (int)Hq, (int)Hk, (int)S, (float)scale, skip.data_ptr<int>(),
+      base.data_ptr<int>(), owner.data_ptr<int>(), (int)Tp);
+  HIP_CHECK_KERNEL();
+  return o;
+}
+
 // ---------------- Paged decode attention ----------------
 torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor kcache,
                                 torch::Tensor vcache, torch::Tensor block_table,
@@ -948,6 +998,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "packed attention, row-major O [Tp, H*D]", pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("vt"), pybind11::arg("scale"), pybind11::arg("skip"),
         pybind11::arg("base"), pybind11::arg("Tp"), pybind11::arg("out") = pybind11::none());
+  m.def("attn_fwd_v5_packed_rm_qkv", &attn_fwd_v5_packed_rm_qkv,
+        "packed attention reading V from the packed qkv rows, row-major O [Tp, Hq*D]",
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("qkv"), pybind11::arg("Hq"),
+        pybind11::arg("Hk"), pybind11::arg("scale"), pybind11::arg("skip"),
+        pybind11::arg("base"), pybind11::arg("owner"), pybind11::arg("Tp"),
+        pybind11::arg("out") = pybind11::none());
   m.def("attn_fwd_v5_packed", &attn_fwd_v5_packed,
         "attn_fwd_v5 skipping shared-prefix query rows; packed O^T [H*D, Tp] out");
   m.def("paged_decode_attn", &paged_decode_attn, "paged decode attention");

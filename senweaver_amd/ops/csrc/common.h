@@ -69,6 +69,18 @@ __device__ __forceinline__ float group_reduce_max(float v) {
   return v;
 }
 
+// Prefix-packed prefill: the packed qkv row that holds token (b, s), or -1
+// where a bad plan names an owner outside [0, B) (the caller drops the row).
+// The layout is described above rope_scatter_body in elemwise.hip.
+static __device__ __forceinline__ long long packed_src_row(
+    int b, int s, int B, const int* __restrict__ skip,
+    const int* __restrict__ base, const int* __restrict__ owner) {
+  int src_b = b;
+  if (s < skip[b]) src_b = owner[b];
+  if ((unsigned)src_b >= (unsigned)B) return -1;  // bad plan: caller drops it
+  return (long long)base[src_b] + s;
+}
+
 #define HIP_CHECK_KERNEL()                                     \
   do {                                                         \
     hipError_t e = hipGetLastError();                          \

@@ -118,14 +118,7 @@ rope_fwd_kernel(ushort* __restrict__ q, ushort* __restrict__ k,
 // The grid still runs over the B*S OUTPUT rows, so the prefix is broadcast
 // to every member and q_out/k_out are fully written.
 // ---------------------------------------------------------------------------
-static __device__ __forceinline__ long long packed_src_row(
-    int b, int s, int B, const int* __restrict__ skip,
-    const int* __restrict__ base, const int* __restrict__ owner) {
-  int src_b = b;
-  if (s < skip[b]) src_b = owner[b];
-  if ((unsigned)src_b >= (unsigned)B) return -1;  // bad plan: caller drops it
-  return (long long)base[src_b] + s;
-}
+// packed_src_row (common.h) is that rule.
 
 template <bool PACKED>
 static __device__ __forceinline__ void rope_scatter_body(

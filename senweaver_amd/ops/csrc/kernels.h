@@ -156,6 +156,13 @@ SW_KERNEL attn_fwd_v5_packed_rm_kernel(const ushort* Q, const ushort* K,
                                        int H, int Hk, int S, float scale,
                                        const int* skip, const int* base,
                                        int Tp);
+SW_KERNEL attn_fwd_v5_packed_rm_qkv_kernel(const ushort* Q, const ushort* K,
+                                           const ushort* qkv, long long ld,
+                                           long long v_off, long long Tq,
+                                           ushort* O, int B, int H, int Hk,
+                                           int S, float scale, const int* skip,
+                                           const int* base, const int* owner,
+                                           int Tp);
 
 // ---- decode_attention.hip, paged_prefill_attention.hip ----
 SW_KERNEL paged_decode_attn_partial_kernel(const ushort* Q, const ushort* Kcache,
